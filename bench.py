@@ -18,8 +18,11 @@ its full wire bytes from HBM, so the timed work is identical to 1250
 distinct updates. Mask material (clients' work in the real protocol) is
 prepared untimed.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   For N>1 launch under torch.distributed.run (one rank per GPU, RCCL).
+  A plain run sets up, warms up, times K rounds and prints one JSON result
+  line; --dump-outputs DIR also saves the last round's model, and --full adds
+  the checks that the headline figure does not need.
 """
 import argparse
 import json
@@ -51,7 +54,21 @@ def main():
                          "through the production serve plane (delegates to "
                          "scripts/ingest_bench.py; N=1 only)")
     ap.add_argument("--verify", action="store_true", help="small-scale correctness check first")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure (today: the "
+                         "--verify small-scale correctness check); a plain run only "
+                         "sets up, warms up, times --steps rounds and prints the result")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed round "
+                         "returned (the unmasked global model) to DIR/weights.npy; "
+                         "outputs above the size cap are a fixed seeded sample")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.full:
+        args.verify = True
+    if args.ingest and args.dump_outputs is not None:
+        ap.error("--dump-outputs is not available with --ingest")
 
     if args.ingest:
         script = os.path.join(os.path.dirname(os.path.abspath(__file__)),
@@ -212,6 +229,7 @@ def main():
     sanity = float(out.float().abs().mean().item())
     ms_per_step = elapsed / args.steps * 1000.0
     updates_per_sec = total_clients_per_round * args.steps / elapsed
+    _dump_outputs(args, rank, out)
 
     mode = "h2d-overlap " if args.h2d else ""
     collective = {"values_rs": "rccl values-reduce-scatter/all-gather",
@@ -224,6 +242,35 @@ def main():
           mode=mode)
     if world > 1:
         dist.destroy_process_group()
+
+
+# --dump-outputs cap: 8M elements is 32 MB as float32, 64 MB as float64
+DUMP_MAX_ELEMS = 8_000_000
+DUMP_SAMPLE_SEED = 0x5EED
+
+
+def _dump_outputs(args, rank, out):
+    """Write the model the last timed round returned to DIR/weights.npy
+    (float32 for an f32 model, float64 otherwise). The seeds, and so the
+    inputs, depend only on the arguments, so two builds run with the same
+    arguments can be compared element for element. A model longer than
+    DUMP_MAX_ELEMS is reduced to a fixed seeded sample of its elements (sorted
+    indices, drawn with replacement), identical from run to run."""
+    if args.dump_outputs is None or rank != 0:
+        return
+    import numpy as np
+    import torch
+
+    flat = out.reshape(-1)
+    if flat.numel() > DUMP_MAX_ELEMS:
+        idx = np.random.default_rng(DUMP_SAMPLE_SEED).integers(
+            0, flat.numel(), DUMP_MAX_ELEMS, dtype=np.int64)
+        idx.sort()
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    arr = flat.cpu().numpy()
+    arr = arr.astype(np.float32 if arr.dtype == np.float32 else np.float64, copy=False)
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    np.save(os.path.join(args.dump_outputs, "weights.npy"), arr)
 
 
 def _emit(args, rank, world, updates_per_sec, ms_per_step, total_clients, sanity, parallelism,
@@ -325,6 +372,7 @@ def _run_stream(args, eng, cfg, rank, world, dist, device):
         elapsed = float(t.item())
 
     sanity = float(out.float().abs().mean().item())
+    _dump_outputs(args, rank, out)
     _emit(args, rank, world, total_clients * args.steps / elapsed,
           elapsed / args.steps * 1000.0, total_clients, sanity,
           parallelism=f"client-sharded dp{world} + rccl {sharded.strategy}",
