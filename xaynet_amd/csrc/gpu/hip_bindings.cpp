@@ -51,17 +51,18 @@ hipError_t xhip_k4_unmask_values_i32(const uint64_t*, const uint64_t*, int32_t*,
                                      uint64_t, uint64_t, double, double);
 hipError_t xhip_k4_unmask_values_i64(const uint64_t*, const uint64_t*, int64_t*, uint64_t,
                                      uint64_t, uint64_t, double, double);
-hipError_t xhip_k2_canonicalize_u128(const uint64_t*, uint64_t*, uint64_t*, uint64_t, int,
+hipError_t xhip_k2_canonicalize_u128(const uint64_t*, uint64_t*, uint64_t*, uint64_t, int, int,
                                      uint64_t, uint64_t);
+hipError_t xhip_add_u128_to_planes(uint64_t*, const uint64_t*, const uint64_t*, uint64_t, int,
+                                   int);
+hipError_t xhip_k2_recode_planes_u128(const uint64_t*, uint64_t*, uint64_t, int, uint64_t,
+                                      uint64_t, int, int);
 hipError_t xhip_k2_mod_add_u128(uint64_t*, uint64_t*, const uint64_t*, const uint64_t*, uint64_t,
                                 uint64_t, uint64_t);
 hipError_t xhip_k6_unpack_u128(const uint8_t*, uint64_t*, uint64_t*, uint64_t, int);
-hipError_t xhip_k4_unmask_u128_f64(const uint64_t*, const uint64_t*, const uint64_t*, double*,
-                                   uint64_t, int, uint64_t, uint64_t, uint64_t, uint64_t, double,
-                                   double);
-hipError_t xhip_k4_unmask_u128_f32(const uint64_t*, const uint64_t*, const uint64_t*, float*,
-                                   uint64_t, int, uint64_t, uint64_t, uint64_t, uint64_t, double,
-                                   double);
+hipError_t xhip_k4_unmask_u128(const uint64_t*, const uint64_t*, const uint64_t*, void*, uint64_t,
+                               int, int, uint64_t, uint64_t, uint64_t, uint64_t, double, double,
+                               int);
 hipError_t xhip_k1_candidates_u128(const uint32_t*, uint64_t, uint64_t, uint64_t, int, int,
                                    uint64_t, uint64_t, uint64_t*, uint64_t*, uint32_t*, int,
                                    uint32_t*);
@@ -452,15 +453,42 @@ PYBIND11_MODULE(_hip, m) {
     m.def(
         "canonicalize_u128",
         [](uintptr_t acc, uintptr_t out_lo, uintptr_t out_hi, uint64_t len, int n_digits,
-           const std::string& order_dec) {
+           const std::string& order_dec, int digit_bits) {
             auto o = parse_u128(order_dec);
             check(xhip_k2_canonicalize_u128(reinterpret_cast<const uint64_t*>(acc),
                                             reinterpret_cast<uint64_t*>(out_lo),
                                             reinterpret_cast<uint64_t*>(out_hi), len, n_digits,
-                                            uint64_t(o), uint64_t(o >> 64)),
+                                            digit_bits, uint64_t(o), uint64_t(o >> 64)),
                   "k2_canonicalize_u128");
         },
+        py::arg("acc"), py::arg("out_lo"), py::arg("out_hi"), py::arg("len"),
+        py::arg("n_digits"), py::arg("order"), py::arg("digit_bits") = 32,
         py::call_guard<py::gil_scoped_release>());
+    // canonical lo/hi values -> add into k planes of digit_bits-wide digits
+    m.def(
+        "add_u128_to_planes",
+        [](uintptr_t planes, uintptr_t lo, uintptr_t hi, uint64_t len, int k, int digit_bits) {
+            check(xhip_add_u128_to_planes(reinterpret_cast<uint64_t*>(planes),
+                                          reinterpret_cast<const uint64_t*>(lo),
+                                          reinterpret_cast<const uint64_t*>(hi), len, k,
+                                          digit_bits),
+                  "add_u128_to_planes");
+        },
+        py::arg("planes"), py::arg("lo"), py::arg("hi"), py::arg("len"), py::arg("k"),
+        py::arg("digit_bits") = 32, py::call_guard<py::gil_scoped_release>());
+    // 32-bit accumulator planes -> k compact planes of the value mod order
+    m.def(
+        "recode_planes_u128",
+        [](uintptr_t acc, uintptr_t out, uint64_t len, int n_digits,
+           const std::string& order_dec, int k, int digit_bits) {
+            auto o = parse_u128(order_dec);
+            check(xhip_k2_recode_planes_u128(reinterpret_cast<const uint64_t*>(acc),
+                                             reinterpret_cast<uint64_t*>(out), len, n_digits,
+                                             uint64_t(o), uint64_t(o >> 64), k, digit_bits),
+                  "k2_recode_planes_u128");
+        },
+        py::arg("acc"), py::arg("out"), py::arg("len"), py::arg("n_digits"), py::arg("order"),
+        py::arg("k"), py::arg("digit_bits"), py::call_guard<py::gil_scoped_release>());
     m.def(
         "mod_add_u128",
         [](uintptr_t a_lo, uintptr_t a_hi, uintptr_t b_lo, uintptr_t b_hi, uint64_t len,
@@ -487,28 +515,21 @@ PYBIND11_MODULE(_hip, m) {
         "unmask_u128",
         [](uintptr_t acc, uintptr_t mask_lo, uintptr_t mask_hi, uintptr_t out, uint64_t len,
            int n_digits, const std::string& order_dec, const std::string& exp_dec,
-           double n_add_shift, double scalar_sum, int dtype) {
+           double n_add_shift, double scalar_sum, int dtype, int digit_bits) {
+            if (dtype < 0 || dtype > 3) throw std::runtime_error("bad dtype");
             auto o = parse_u128(order_dec);
             auto e = parse_u128(exp_dec);
-            hipError_t rc;
-            if (dtype == 1)
-                rc = xhip_k4_unmask_u128_f64(
-                    reinterpret_cast<const uint64_t*>(acc),
-                    reinterpret_cast<const uint64_t*>(mask_lo),
-                    reinterpret_cast<const uint64_t*>(mask_hi), reinterpret_cast<double*>(out),
-                    len, n_digits, uint64_t(o), uint64_t(o >> 64), uint64_t(e),
-                    uint64_t(e >> 64), n_add_shift, scalar_sum);
-            else if (dtype == 0)
-                rc = xhip_k4_unmask_u128_f32(
-                    reinterpret_cast<const uint64_t*>(acc),
-                    reinterpret_cast<const uint64_t*>(mask_lo),
-                    reinterpret_cast<const uint64_t*>(mask_hi), reinterpret_cast<float*>(out),
-                    len, n_digits, uint64_t(o), uint64_t(o >> 64), uint64_t(e),
-                    uint64_t(e >> 64), n_add_shift, scalar_sum);
-            else
-                throw std::runtime_error("u128 unmask supports f32/f64 outputs");
-            check(rc, "k4_unmask_u128");
+            check(xhip_k4_unmask_u128(reinterpret_cast<const uint64_t*>(acc),
+                                      reinterpret_cast<const uint64_t*>(mask_lo),
+                                      reinterpret_cast<const uint64_t*>(mask_hi),
+                                      reinterpret_cast<void*>(out), len, n_digits, digit_bits,
+                                      uint64_t(o), uint64_t(o >> 64), uint64_t(e),
+                                      uint64_t(e >> 64), n_add_shift, scalar_sum, dtype),
+                  "k4_unmask_u128");
         },
+        py::arg("acc"), py::arg("mask_lo"), py::arg("mask_hi"), py::arg("out"), py::arg("len"),
+        py::arg("n_digits"), py::arg("order"), py::arg("exp_shift"), py::arg("n_add_shift"),
+        py::arg("scalar_sum"), py::arg("dtype"), py::arg("digit_bits") = 32,
         py::call_guard<py::gil_scoped_release>());
 
     m.def(

@@ -1015,29 +1015,78 @@ __device__ __forceinline__ unsigned __int128 u192_mod_u128(u192 v, unsigned __in
     return ((unsigned __int128)v.w[1] << 64) | v.w[0];
 }
 
-// digit planes -> canonical split u64 planes mod order
-extern "C" __global__ void k2_canonicalize_u128(
-    const uint64_t* __restrict__ acc, uint64_t* __restrict__ out_lo,
-    uint64_t* __restrict__ out_hi, uint64_t len, int n_digits,
-    uint64_t order_lo, uint64_t order_hi) {
-    uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (i >= len) return;
+// Recombine `n_planes` digit planes (plane stride `len`) into one u192:
+// v = sum_d plane[d][i] << (digit_bits * d), built top-down as
+// v = (v << digit_bits) + plane[d][i] with carry. digit_bits is 1..63; the
+// planes hold plain integer SUMS of digits, so a plane entry may exceed
+// 2^digit_bits. The caller guarantees the total stays inside the u192_mod_u128
+// window (accumulator: < 2^160; cross-rank compact planes: < world * order).
+// DB is the compile-time digit width (32 for the accumulator), 0 = runtime.
+template <int DB>
+__device__ __forceinline__ u192 u192_from_planes(const uint64_t* __restrict__ planes,
+                                                 uint64_t len, uint64_t i, int n_planes,
+                                                 int digit_bits) {
+    const int s = DB ? DB : digit_bits;
     u192 v{{0, 0, 0}};
-    for (int d = n_digits - 1; d >= 0; --d) {
-        // v = (v << 32) + digit
-        v.w[2] = (v.w[2] << 32) | (v.w[1] >> 32);
-        v.w[1] = (v.w[1] << 32) | (v.w[0] >> 32);
-        v.w[0] = (v.w[0] << 32);
-        unsigned __int128 s = (unsigned __int128)v.w[0] + acc[uint64_t(d) * len + i];
-        v.w[0] = uint64_t(s);
-        if (s >> 64) {  // carry
+    for (int d = n_planes - 1; d >= 0; --d) {
+        v.w[2] = (v.w[2] << s) | (v.w[1] >> (64 - s));
+        v.w[1] = (v.w[1] << s) | (v.w[0] >> (64 - s));
+        v.w[0] = (v.w[0] << s);
+        unsigned __int128 t = (unsigned __int128)v.w[0] + planes[uint64_t(d) * len + i];
+        v.w[0] = uint64_t(t);
+        if (t >> 64) {  // carry
             if (++v.w[1] == 0) ++v.w[2];
         }
     }
+    return v;
+}
+
+// digit planes -> canonical split u64 planes mod order
+template <int DB>
+__global__ void k2_canonicalize_u128(
+    const uint64_t* __restrict__ acc, uint64_t* __restrict__ out_lo,
+    uint64_t* __restrict__ out_hi, uint64_t len, int n_digits, int digit_bits,
+    uint64_t order_lo, uint64_t order_hi) {
+    uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= len) return;
+    u192 v = u192_from_planes<DB>(acc, len, i, n_digits, digit_bits);
     unsigned __int128 order = ((unsigned __int128)order_hi << 64) | order_lo;
     unsigned __int128 r = u192_mod_u128(v, order);
     out_lo[i] = uint64_t(r);
     out_hi[i] = uint64_t(r >> 64);
+}
+
+// Digit j (digit_bits wide) of a u128 value; digits may straddle the lo/hi
+// word boundary. Shifts of 128 or more (k * digit_bits may overshoot) are 0.
+__device__ __forceinline__ uint64_t u128_digit(unsigned __int128 v, int j, int digit_bits) {
+    int sh = digit_bits * j;
+    if (sh >= 128) return 0;
+    return uint64_t(v >> sh) & ((uint64_t(1) << digit_bits) - 1);
+}
+
+// canonical split lo/hi values -> ADD into k planes of digit_bits-wide digits
+// (wide analog of k_add_u64_to_planes)
+extern "C" __global__ void k_add_u128_to_planes(
+    uint64_t* __restrict__ planes, const uint64_t* __restrict__ lo,
+    const uint64_t* __restrict__ hi, uint64_t len, int k, int digit_bits) {
+    uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= len) return;
+    unsigned __int128 v = ((unsigned __int128)hi[i] << 64) | lo[i];
+    for (int j = 0; j < k; ++j) planes[uint64_t(j) * len + i] += u128_digit(v, j, digit_bits);
+}
+
+// Fused re-digitisation for the cross-rank reduce-scatter: 32-bit accumulator
+// planes -> value mod order -> WRITE k planes of digit_bits-wide digits. The
+// canonical lo/hi intermediate stays in registers.
+extern "C" __global__ void k2_recode_planes_u128(
+    const uint64_t* __restrict__ acc, uint64_t* __restrict__ out, uint64_t len, int n_digits,
+    uint64_t order_lo, uint64_t order_hi, int k, int digit_bits) {
+    uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= len) return;
+    u192 v = u192_from_planes<32>(acc, len, i, n_digits, 32);
+    unsigned __int128 order = ((unsigned __int128)order_hi << 64) | order_lo;
+    unsigned __int128 r = u192_mod_u128(v, order);
+    for (int j = 0; j < k; ++j) out[uint64_t(j) * len + i] = u128_digit(r, j, digit_bits);
 }
 
 // split-plane mod-add: a = (a + b) mod order. Both inputs canonical
@@ -1074,27 +1123,22 @@ extern "C" __global__ void k6_unpack_u128(
     out_hi[i] = hi;
 }
 
-// K4 for u128 orders: finalize + unmask into f64/f32 weights.
+// K4 for u128 orders: finalize + unmask into model weights (integer outputs
+// truncate toward zero, as k4_unmask does).
 // y = (t / E) + (t % E)/E - n*add, t = (acc - mask) mod order; E <= 10^20.
-template <typename OUT>
+// `acc` is any contiguous [n_digits][len] plane tensor of digit_bits-wide
+// digit sums (the accumulator, or a reduce-scattered shard of compact
+// planes); mask_lo/mask_hi are independent rows, so a column slice of a
+// [2][n] mask tensor works.
+template <typename OUT, bool TRUNC, int DB>
 __global__ void k4_unmask_u128(
     const uint64_t* __restrict__ acc, const uint64_t* __restrict__ mask_lo,
     const uint64_t* __restrict__ mask_hi, OUT* __restrict__ out, uint64_t len, int n_digits,
-    uint64_t order_lo, uint64_t order_hi, uint64_t exp_lo, uint64_t exp_hi,
+    int digit_bits, uint64_t order_lo, uint64_t order_hi, uint64_t exp_lo, uint64_t exp_hi,
     double n_add_shift, double scalar_sum) {
     uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (i >= len) return;
-    u192 v{{0, 0, 0}};
-    for (int d = n_digits - 1; d >= 0; --d) {
-        v.w[2] = (v.w[2] << 32) | (v.w[1] >> 32);
-        v.w[1] = (v.w[1] << 32) | (v.w[0] >> 32);
-        v.w[0] = (v.w[0] << 32);
-        unsigned __int128 s = (unsigned __int128)v.w[0] + acc[uint64_t(d) * len + i];
-        v.w[0] = uint64_t(s);
-        if (s >> 64) {
-            if (++v.w[1] == 0) ++v.w[2];
-        }
-    }
+    u192 v = u192_from_planes<DB>(acc, len, i, n_digits, digit_bits);
     unsigned __int128 order = ((unsigned __int128)order_hi << 64) | order_lo;
     unsigned __int128 m = u192_mod_u128(v, order);
     unsigned __int128 msk = ((unsigned __int128)mask_hi[i] << 64) | mask_lo[i];
@@ -1117,7 +1161,11 @@ __global__ void k4_unmask_u128(
         e >>= 1;
     }
     double y = double(q) + double(r) / double(E);
-    out[i] = OUT((y - n_add_shift) / scalar_sum);
+    double w = (y - n_add_shift) / scalar_sum;
+    if constexpr (TRUNC)
+        out[i] = OUT(trunc(w));
+    else
+        out[i] = OUT(w);
 }
 
 // K5 wide: synthesize a masked update row for u128 orders (F64 configs:
@@ -1406,12 +1454,41 @@ hipError_t xhip_k3_aggregate(uint64_t* acc, const uint8_t* updates, uint64_t str
     return hipGetLastError();
 }
 
+// digit_bits 32 (the accumulator layout) takes the compile-time variant; any
+// other width in 1..63 the runtime-shift one.
 hipError_t xhip_k2_canonicalize_u128(const uint64_t* acc, uint64_t* out_lo, uint64_t* out_hi,
-                                     uint64_t len, int n_digits, uint64_t order_lo,
-                                     uint64_t order_hi) {
+                                     uint64_t len, int n_digits, int digit_bits,
+                                     uint64_t order_lo, uint64_t order_hi) {
+    if (digit_bits < 1 || digit_bits > 63 || n_digits < 1) return hipErrorInvalidValue;
+    if (len == 0) return hipSuccess;
     uint32_t threads = 256, wgs = ceil_div_u32(len, threads);
-    hipLaunchKernelGGL(k2_canonicalize_u128, dim3(wgs), dim3(threads), 0, 0, acc, out_lo, out_hi,
-                       len, n_digits, order_lo, order_hi);
+    if (digit_bits == 32)
+        hipLaunchKernelGGL((k2_canonicalize_u128<32>), dim3(wgs), dim3(threads), 0, 0, acc,
+                           out_lo, out_hi, len, n_digits, digit_bits, order_lo, order_hi);
+    else
+        hipLaunchKernelGGL((k2_canonicalize_u128<0>), dim3(wgs), dim3(threads), 0, 0, acc,
+                           out_lo, out_hi, len, n_digits, digit_bits, order_lo, order_hi);
+    return hipGetLastError();
+}
+
+hipError_t xhip_add_u128_to_planes(uint64_t* planes, const uint64_t* lo, const uint64_t* hi,
+                                   uint64_t len, int k, int digit_bits) {
+    if (digit_bits < 1 || digit_bits > 63 || k < 1) return hipErrorInvalidValue;
+    if (len == 0) return hipSuccess;
+    uint32_t threads = 256, wgs = ceil_div_u32(len, threads);
+    hipLaunchKernelGGL(k_add_u128_to_planes, dim3(wgs), dim3(threads), 0, 0, planes, lo, hi, len,
+                       k, digit_bits);
+    return hipGetLastError();
+}
+
+hipError_t xhip_k2_recode_planes_u128(const uint64_t* acc, uint64_t* out, uint64_t len,
+                                      int n_digits, uint64_t order_lo, uint64_t order_hi, int k,
+                                      int digit_bits) {
+    if (digit_bits < 1 || digit_bits > 63 || k < 1 || n_digits < 1) return hipErrorInvalidValue;
+    if (len == 0) return hipSuccess;
+    uint32_t threads = 256, wgs = ceil_div_u32(len, threads);
+    hipLaunchKernelGGL(k2_recode_planes_u128, dim3(wgs), dim3(threads), 0, 0, acc, out, len,
+                       n_digits, order_lo, order_hi, k, digit_bits);
     return hipGetLastError();
 }
 
@@ -1432,27 +1509,39 @@ hipError_t xhip_k6_unpack_u128(const uint8_t* in, uint64_t* out_lo, uint64_t* ou
     return hipGetLastError();
 }
 
-hipError_t xhip_k4_unmask_u128_f64(const uint64_t* acc, const uint64_t* mask_lo,
-                                   const uint64_t* mask_hi, double* out, uint64_t len,
-                                   int n_digits, uint64_t order_lo, uint64_t order_hi,
-                                   uint64_t exp_lo, uint64_t exp_hi, double n_add_shift,
-                                   double scalar_sum) {
+// wide K4 launcher: dtype 0=f32 1=f64 2=i32 3=i64 (integers truncate);
+// digit_bits 32 takes the compile-time variant, as above
+hipError_t xhip_k4_unmask_u128(const uint64_t* acc, const uint64_t* mask_lo,
+                               const uint64_t* mask_hi, void* out, uint64_t len, int n_digits,
+                               int digit_bits, uint64_t order_lo, uint64_t order_hi,
+                               uint64_t exp_lo, uint64_t exp_hi, double n_add_shift,
+                               double scalar_sum, int dtype) {
+    if (digit_bits < 1 || digit_bits > 63 || n_digits < 1) return hipErrorInvalidValue;
+    if (len == 0) return hipSuccess;
     uint32_t threads = 256, wgs = ceil_div_u32(len, threads);
-    hipLaunchKernelGGL((k4_unmask_u128<double>), dim3(wgs), dim3(threads), 0, 0, acc, mask_lo,
-                       mask_hi, out, len, n_digits, order_lo, order_hi, exp_lo, exp_hi,
-                       n_add_shift, scalar_sum);
-    return hipGetLastError();
-}
-
-hipError_t xhip_k4_unmask_u128_f32(const uint64_t* acc, const uint64_t* mask_lo,
-                                   const uint64_t* mask_hi, float* out, uint64_t len,
-                                   int n_digits, uint64_t order_lo, uint64_t order_hi,
-                                   uint64_t exp_lo, uint64_t exp_hi, double n_add_shift,
-                                   double scalar_sum) {
-    uint32_t threads = 256, wgs = ceil_div_u32(len, threads);
-    hipLaunchKernelGGL((k4_unmask_u128<float>), dim3(wgs), dim3(threads), 0, 0, acc, mask_lo,
-                       mask_hi, out, len, n_digits, order_lo, order_hi, exp_lo, exp_hi,
-                       n_add_shift, scalar_sum);
+#define K4W(OUT, TRUNC, DB)                                                                  \
+    hipLaunchKernelGGL((k4_unmask_u128<OUT, TRUNC, DB>), dim3(wgs), dim3(threads), 0, 0, acc, \
+                       mask_lo, mask_hi, reinterpret_cast<OUT*>(out), len, n_digits,         \
+                       digit_bits, order_lo, order_hi, exp_lo, exp_hi, n_add_shift,          \
+                       scalar_sum)
+    if (digit_bits == 32) {
+        switch (dtype) {
+            case 0: K4W(float, false, 32); break;
+            case 1: K4W(double, false, 32); break;
+            case 2: K4W(int32_t, true, 32); break;
+            case 3: K4W(int64_t, true, 32); break;
+            default: return hipErrorInvalidValue;
+        }
+    } else {
+        switch (dtype) {
+            case 0: K4W(float, false, 0); break;
+            case 1: K4W(double, false, 0); break;
+            case 2: K4W(int32_t, true, 0); break;
+            case 3: K4W(int64_t, true, 0); break;
+            default: return hipErrorInvalidValue;
+        }
+    }
+#undef K4W
     return hipGetLastError();
 }
 

@@ -1,15 +1,20 @@
 """CPU digit-plane aggregation engine (test/dev analog of the GPU engine).
 
-Mirrors the `GpuMaskedAggregator` API (u64-order configs) with numpy so the
-multi-process serve plane and the gloo world>1 tests can run the EXACT same
-composition code (`xaynet_amd.parallel.ShardedAggregation`, worker loop,
-ingest ring) on boxes without a GPU. Production deployments use the HIP
-engine; this class exists so the distributed path is provable in CPU CI
-(VERDICT r01 items 1 and 10).
+Mirrors the `GpuMaskedAggregator` API with numpy so the multi-process serve
+plane and the gloo world>1 tests can run the EXACT same composition code
+(`xaynet_amd.parallel.ShardedAggregation`, worker loop, ingest ring) on boxes
+without a GPU. Production deployments use the HIP engine; this class exists
+so the distributed path is provable in CPU CI.
+
+u64 orders use vectorised numpy u64 math. Wide orders (2^64 <= order <=
+2^128, bpn 9..16) use the GPU engine's layouts — canonical values as
+[2, length] lo/hi int64 tensors, compact digit planes of `digit_bits`-wide
+digits — and Python-int/object math internally: a test vehicle, not a hot
+path.
 
 Semantics are pinned to the reference math (masking.rs:190-231, 292-316):
 plane arithmetic is the same deferred-modular scheme as kernels.hip, and the
-unmask formula matches the K4 kernel (including its float order of
+unmask formula matches the K4 kernels (including their float order of
 operations) so CPU- and GPU-plane results agree on integer dtypes.
 """
 from __future__ import annotations
@@ -20,24 +25,25 @@ import torch
 from xaynet_amd import _core
 
 _U64 = np.uint64
+_M64 = (1 << 64) - 1
 
 
 class CpuPlaneAggregator:
     """Digit-plane aggregation of wire-format masked updates on the CPU."""
 
-    wide = False
-
     _TORCH_DTYPES = {0: torch.float32, 1: torch.float64, 2: torch.int32, 3: torch.int64}
     _NP_DTYPES = {0: np.float32, 1: np.float64, 2: np.int32, 3: np.int64}
 
     def __init__(self, vect_cfg, unit_cfg, length: int, device: str = "cpu"):
-        if not vect_cfg.order_fits_u64:
-            raise ValueError("CpuPlaneAggregator covers u64 orders only")
+        if vect_cfg.bytes_per_number > 16:
+            raise ValueError("CpuPlaneAggregator covers group orders up to 2^128 "
+                             f"(got {vect_cfg.bytes_per_number} bytes/element)")
         self.vect_cfg = vect_cfg
         self.unit_cfg = unit_cfg
         self.length = length
         self.device = torch.device("cpu")
         self.bpn = vect_cfg.bytes_per_number
+        self.wide = not vect_cfg.order_fits_u64
         self.n_digits = (self.bpn + 3) // 4
         self.order = vect_cfg.order
         self.order_int = int(vect_cfg.order)
@@ -59,32 +65,63 @@ class CpuPlaneAggregator:
         t = torch.frombuffer(bytearray(wire_limbs), dtype=torch.uint8)
         pool[row, : t.numel()].copy_(t)
 
-    # ---------------- limb <-> value ----------------
+    # ---------------- value tensors <-> python ints ----------------
 
-    def _rows_to_values(self, rows: np.ndarray) -> np.ndarray:
-        """uint8 [n, >=length*bpn] -> u64 [n, length] little-endian limbs."""
-        n = rows.shape[0]
-        limbs = rows[:, : self.length * self.bpn].reshape(n, self.length, self.bpn)
-        vals = np.zeros((n, self.length), dtype=_U64)
-        for b in range(self.bpn):
-            vals |= limbs[:, :, b].astype(_U64) << _U64(8 * b)
-        return vals
+    def _ints(self, vals: torch.Tensor) -> np.ndarray:
+        """Canonical value tensor ([n], or wide [2, n] lo/hi) -> object ints."""
+        if self.wide:
+            lo = vals[0].numpy().view(_U64).astype(object)
+            hi = vals[1].numpy().view(_U64).astype(object)
+            return (hi << 64) + lo
+        return vals.numpy().view(_U64).astype(object)
 
-    def unpack_wire(self, packed: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
-        rows = packed.numpy().reshape(1, -1)
-        vals = self._rows_to_values(rows)[0]
-        t = torch.from_numpy(vals.astype(np.int64))
+    def _values(self, ints: np.ndarray) -> torch.Tensor:
+        """Object ints -> canonical value tensor (inverse of _ints)."""
+        if self.wide:
+            lo = np.array([int(v) & _M64 for v in ints], dtype=_U64)
+            hi = np.array([int(v) >> 64 for v in ints], dtype=_U64)
+            return torch.from_numpy(np.stack([lo, hi]).astype(np.int64))
+        return torch.from_numpy(np.array([int(v) for v in ints], dtype=_U64).astype(np.int64))
+
+    @staticmethod
+    def _ret(t: torch.Tensor, out: torch.Tensor | None) -> torch.Tensor:
         if out is None:
             return t
         out.copy_(t)
         return out
 
+    # ---------------- limb <-> value ----------------
+
+    def _limb_word(self, limbs: np.ndarray, first: int, last: int) -> np.ndarray:
+        """Little-endian bytes [first, last) of [..., bpn] limbs -> u64."""
+        word = np.zeros(limbs.shape[:-1], dtype=_U64)
+        for b in range(first, min(last, self.bpn)):
+            word |= limbs[..., b].astype(_U64) << _U64(8 * (b - first))
+        return word
+
+    def _rows_to_values(self, rows: np.ndarray) -> np.ndarray:
+        """uint8 [n, >=length*bpn] -> u64 [n, length] little-endian limbs."""
+        n = rows.shape[0]
+        limbs = rows[:, : self.length * self.bpn].reshape(n, self.length, self.bpn)
+        return self._limb_word(limbs, 0, 8)
+
+    def _limbs_to_tensor(self, limbs: np.ndarray) -> torch.Tensor:
+        """uint8 [length, bpn] -> canonical value tensor."""
+        lo = self._limb_word(limbs, 0, 8)
+        if self.wide:
+            lo = np.stack([lo, self._limb_word(limbs, 8, 16)])
+        return torch.from_numpy(lo.astype(np.int64))
+
+    def unpack_wire(self, packed: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+        limbs = packed.numpy()[: self.length * self.bpn].reshape(self.length, self.bpn)
+        return self._ret(self._limbs_to_tensor(limbs), out)
+
     def pack_wire(self, values: torch.Tensor) -> torch.Tensor:
-        vals = values.numpy().astype(_U64)
+        words = values.numpy().view(_U64).reshape(-1, self.length)  # [1 or 2, length]
         out = np.zeros(self.length * self.bpn, dtype=np.uint8)
         limbs = out.reshape(self.length, self.bpn)
         for b in range(self.bpn):
-            limbs[:, b] = ((vals >> _U64(8 * b)) & _U64(0xFF)).astype(np.uint8)
+            limbs[:, b] = ((words[b // 8] >> _U64(8 * (b % 8))) & _U64(0xFF)).astype(np.uint8)
         return torch.from_numpy(out)
 
     # ---------------- mask expansion ----------------
@@ -92,15 +129,8 @@ class CpuPlaneAggregator:
     def derive_mask_values(self, seed: bytes, out: torch.Tensor | None = None) -> torch.Tensor:
         pair = _core.mask.MaskConfigPair(self.vect_cfg, self.unit_cfg)
         obj = _core.mask.derive_mask(seed, self.length, pair)
-        vals = np.frombuffer(obj.vect_bytes, dtype=np.uint8).reshape(self.length, self.bpn)
-        v = np.zeros(self.length, dtype=_U64)
-        for b in range(self.bpn):
-            v |= vals[:, b].astype(_U64) << _U64(8 * b)
-        t = torch.from_numpy(v.astype(np.int64))
-        if out is None:
-            return t
-        out.copy_(t)
-        return out
+        limbs = np.frombuffer(obj.vect_bytes, dtype=np.uint8).reshape(self.length, self.bpn)
+        return self._ret(self._limbs_to_tensor(limbs), out)
 
     def unit_draw(self, seed: bytes) -> int:
         v, _ = _core.mask.unit_draw(seed, self.unit_cfg)
@@ -110,32 +140,50 @@ class CpuPlaneAggregator:
 
     def aggregate_pool(self, pool: torch.Tensor, n_updates: int, unit_sum: int = 0):
         rows = pool[:n_updates].numpy()
-        vals = self._rows_to_values(rows)
         acc = self.acc.numpy().view(_U64)
-        for d in range(self.n_digits):
-            acc[d] += ((vals >> _U64(32 * d)) & _U64(0xFFFFFFFF)).sum(axis=0, dtype=_U64)
+        if self.wide:
+            limbs = rows[:, : self.length * self.bpn].reshape(n_updates, self.length, self.bpn)
+            for d in range(self.n_digits):
+                acc[d] += self._limb_word(limbs, 4 * d, 4 * d + 4).sum(axis=0, dtype=_U64)
+        else:
+            vals = self._rows_to_values(rows)
+            for d in range(self.n_digits):
+                acc[d] += ((vals >> _U64(32 * d)) & _U64(0xFFFFFFFF)).sum(axis=0, dtype=_U64)
         self.nb_models += n_updates
         self.unit_acc = (self.unit_acc + unit_sum) % int(self.unit_cfg.order)
 
     # ---------------- finalize / unmask ----------------
 
-    def _planes_to_u64(self, planes: torch.Tensor) -> np.ndarray:
+    def _check_digits(self, digit_bits: int):
+        if not 1 <= digit_bits <= 63:
+            raise ValueError("digit_bits must be in 1..63")
+        if not self.wide and digit_bits != 32:
+            raise ValueError("u64-order digit planes are 32 bits wide")
+
+    def _planes_to_ints(self, planes: torch.Tensor, digit_bits: int = 32) -> np.ndarray:
         """Recombine digit planes mod order (object math: digits may carry)."""
+        self._check_digits(digit_bits)
         arr = planes.numpy().view(_U64)
         total = np.zeros(arr.shape[1], dtype=object)
         for d in reversed(range(planes.shape[0])):
-            total = (total << 32) + arr[d].astype(object)
-        return np.array([int(v) % self.order_int for v in total], dtype=_U64)
+            total = (total << digit_bits) + arr[d].astype(object)
+        return total % self.order_int
+
+    def _add_ints_to_planes(self, ints: np.ndarray, planes: torch.Tensor, digit_bits: int):
+        self._check_digits(digit_bits)
+        acc = planes.numpy().view(_U64)
+        digit_mask = (1 << digit_bits) - 1
+        for d in range(planes.shape[0]):
+            acc[d] += np.array([(int(v) >> (digit_bits * d)) & digit_mask for v in ints],
+                               dtype=_U64)
 
     def canonical(self, out: torch.Tensor | None = None) -> torch.Tensor:
-        vals = self._planes_to_u64(self.acc)
-        t = torch.from_numpy(vals.astype(np.int64))
-        if out is None:
-            return t
-        out.copy_(t)
-        return out
+        return self._ret(self._values(self._planes_to_ints(self.acc)), out)
 
     def mod_add_values(self, a: torch.Tensor, b: torch.Tensor):
+        if self.wide:
+            a.copy_(self._values((self._ints(a) + self._ints(b)) % self.order_int))
+            return
         av = a.numpy().view(_U64)
         bv = b.numpy().view(_U64)
         order = _U64(self.order_int)
@@ -145,14 +193,29 @@ class CpuPlaneAggregator:
     def add_values_to_planes(self, vals: torch.Tensor):
         self.values_to_planes(vals, self.acc)
 
-    def values_to_planes(self, vals: torch.Tensor, planes: torch.Tensor):
+    def values_to_planes(self, vals: torch.Tensor, planes: torch.Tensor, digit_bits: int = 32):
+        """Add canonical values into [k, n] planes of digit_bits-wide digits."""
+        if self.wide:
+            self._add_ints_to_planes(self._ints(vals), planes, digit_bits)
+            return
+        self._check_digits(digit_bits)
         v = vals.numpy().view(_U64)
         acc = planes.numpy().view(_U64)
         for d in range(planes.shape[0]):
             acc[d] += (v >> _U64(32 * d)) & _U64(0xFFFFFFFF)
 
-    def planes_to_values(self, planes: torch.Tensor, out: torch.Tensor):
-        out.copy_(torch.from_numpy(self._planes_to_u64(planes).astype(np.int64)))
+    def planes_to_values(self, planes: torch.Tensor, out: torch.Tensor, digit_bits: int = 32):
+        out.copy_(self._values(self._planes_to_ints(planes, digit_bits)))
+
+    def recode_planes(self, out_planes: torch.Tensor, digit_bits: int) -> torch.Tensor:
+        """Write the accumulator's value mod order into compact [k, length]
+        planes of digit_bits-wide digits (wide orders)."""
+        if not self.wide:
+            raise NotImplementedError("compact digit planes cover wide (u128) orders; "
+                                      "u64 orders reduce canonical values or 32-bit planes")
+        out_planes.zero_()
+        self._add_ints_to_planes(self._planes_to_ints(self.acc), out_planes, digit_bits)
+        return out_planes
 
     def _scalar_sum(self, mask_unit: int, nb: int) -> float:
         from .engine import _cfg_scalars
@@ -166,15 +229,22 @@ class CpuPlaneAggregator:
 
     def _finalize(self, masked: np.ndarray, mask: np.ndarray, nb: int, scalar_sum: float,
                   dt: int) -> torch.Tensor:
+        """masked/mask: object-int arrays of canonical values."""
         from .engine import _cfg_scalars
 
         vinfo = _cfg_scalars(self.vect_cfg)
         order = self.order_int
-        t = (masked.astype(object) + order - mask.astype(object)) % order
-        # mirror K4: float(t)/exp_shift - nb*add_shift, then / scalar_sum
+        t = (masked + order - mask) % order
         exp = vinfo["exp_shift_u64"]
-        outf = np.array([(int(v) / exp - nb * vinfo["add_shift"]) / scalar_sum
-                         for v in t], dtype=np.float64)
+        n_add = nb * vinfo["add_shift"]
+        if self.wide:
+            # mirror k4_unmask_u128: double(t / E) + double(t % E) / double(E)
+            outf = np.array([(float(int(v) // exp) + float(int(v) % exp) / float(exp) - n_add)
+                             / scalar_sum for v in t], dtype=np.float64)
+        else:
+            # mirror K4: float(t)/exp_shift - nb*add_shift, then / scalar_sum
+            outf = np.array([(int(v) / exp - n_add) / scalar_sum for v in t],
+                            dtype=np.float64)
         np_dt = self._NP_DTYPES[dt]
         if dt in (2, 3):
             outf = np.trunc(outf)
@@ -184,24 +254,25 @@ class CpuPlaneAggregator:
                nb_models: int | None = None, dtype: int | None = None) -> torch.Tensor:
         nb = self.nb_models if nb_models is None else nb_models
         dt = self.vect_cfg.dtype if dtype is None else dtype
-        masked = self._planes_to_u64(self.acc)
-        return self._finalize(masked, mask_values.numpy().view(_U64), nb,
+        masked = self._planes_to_ints(self.acc)
+        return self._finalize(masked, self._ints(mask_values), nb,
                               self._scalar_sum(mask_unit, nb), dt)
 
     def unmask_values(self, vals: torch.Tensor, mask_values: torch.Tensor, mask_unit: int,
                       nb_models: int, dtype: int | None = None) -> torch.Tensor:
+        if self.wide:
+            raise NotImplementedError("values unmask covers u64 orders")
         dt = self.vect_cfg.dtype if dtype is None else dtype
-        order = self.order_int
-        masked = np.array([int(v) % order for v in vals.numpy().view(_U64).astype(object)],
-                          dtype=_U64)
-        return self._finalize(masked, mask_values.numpy().view(_U64), nb_models,
+        masked = vals.numpy().view(_U64).astype(object) % self.order_int
+        return self._finalize(masked, self._ints(mask_values), nb_models,
                               self._scalar_sum(mask_unit, nb_models), dt)
 
     def unmask_planes(self, planes: torch.Tensor, mask_values: torch.Tensor, mask_unit: int,
-                      nb_models: int, dtype: int | None = None) -> torch.Tensor:
+                      nb_models: int, dtype: int | None = None,
+                      digit_bits: int = 32) -> torch.Tensor:
         dt = self.vect_cfg.dtype if dtype is None else dtype
-        masked = self._planes_to_u64(planes)
-        return self._finalize(masked, mask_values.numpy().view(_U64), nb_models,
+        masked = self._planes_to_ints(planes, digit_bits)
+        return self._finalize(masked, self._ints(mask_values), nb_models,
                               self._scalar_sum(mask_unit, nb_models), dt)
 
     def reset(self):

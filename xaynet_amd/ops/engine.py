@@ -56,7 +56,7 @@ class GpuMaskedAggregator:
         self.device = torch.device(device)
         self.bpn = vect_cfg.bytes_per_number
         # wide (u128-order) configs: canonical values are split lo/hi u64
-        # planes; K1/K5 (mask synthesis) stay off-GPU for these
+        # planes; every kernel (K1..K6) has a u128 variant
         self.wide = not vect_cfg.order_fits_u64
         self.n_digits = (self.bpn + 3) // 4
         self.order = vect_cfg.order  # decimal string
@@ -152,14 +152,43 @@ class GpuMaskedAggregator:
     def add_values_to_planes(self, vals: torch.Tensor):
         _hip.add_u64_to_planes(self.acc.data_ptr(), vals.data_ptr(), self.length, self.n_digits)
 
-    def values_to_planes(self, vals: torch.Tensor, planes: torch.Tensor):
-        """Add canonical u64 values into an arbitrary [n_digits, n] plane tensor."""
+    def values_to_planes(self, vals: torch.Tensor, planes: torch.Tensor, digit_bits: int = 32):
+        """Add canonical values into an arbitrary contiguous plane tensor.
+        u64 orders: [n] values into [n_digits, n] 32-bit digit planes. Wide
+        orders: [2, n] lo/hi values into [k, n] planes of digit_bits-wide
+        digits (k = planes.shape[0])."""
+        if self.wide:
+            _check_wide_planes(planes, vals)
+            _hip.add_u128_to_planes(planes.data_ptr(), vals[0].data_ptr(), vals[1].data_ptr(),
+                                    planes.shape[1], planes.shape[0], digit_bits)
+            return
+        _check_u64_digits(digit_bits)
         _hip.add_u64_to_planes(planes.data_ptr(), vals.data_ptr(), vals.numel(), self.n_digits)
 
-    def planes_to_values(self, planes: torch.Tensor, out: torch.Tensor):
-        """Canonicalize an arbitrary [n_digits, n] plane tensor mod order."""
+    def planes_to_values(self, planes: torch.Tensor, out: torch.Tensor, digit_bits: int = 32):
+        """Canonicalize an arbitrary contiguous plane tensor mod order (the
+        inverse layout of values_to_planes; wide `out` is [2, n] lo/hi)."""
+        if self.wide:
+            _check_wide_planes(planes, out)
+            _hip.canonicalize_u128(planes.data_ptr(), out[0].data_ptr(), out[1].data_ptr(),
+                                   planes.shape[1], planes.shape[0], self.order, digit_bits)
+            return
+        _check_u64_digits(digit_bits)
         _hip.canonicalize(planes.data_ptr(), out.data_ptr(), out.numel(),
                           self.n_digits, self.order)
+
+    def recode_planes(self, out_planes: torch.Tensor, digit_bits: int) -> torch.Tensor:
+        """Write (not add) the accumulator's value mod order into the compact
+        [k, length] planes of digit_bits-wide digits — the wide-order input of
+        the cross-rank reduce-scatter (xaynet_amd.parallel.compact_digits)."""
+        if not self.wide:
+            raise NotImplementedError("compact digit planes cover wide (u128) orders; "
+                                      "u64 orders reduce canonical values or 32-bit planes")
+        if out_planes.shape[1] != self.length or not out_planes.is_contiguous():
+            raise ValueError("out_planes must be a contiguous [k, length] tensor")
+        _hip.recode_planes_u128(self.acc.data_ptr(), out_planes.data_ptr(), self.length,
+                                self.n_digits, self.order, out_planes.shape[0], digit_bits)
+        return out_planes
 
     _TORCH_DTYPES = {0: torch.float32, 1: torch.float64, 2: torch.int32, 3: torch.int64}
 
@@ -218,12 +247,12 @@ class GpuMaskedAggregator:
         return out
 
     def unmask_planes(self, planes: torch.Tensor, mask_values: torch.Tensor, mask_unit: int,
-                      nb_models: int, dtype: int | None = None) -> torch.Tensor:
-        """Unmask an arbitrary contiguous [n_digits, n] digit-plane tensor
+                      nb_models: int, dtype: int | None = None,
+                      digit_bits: int = 32) -> torch.Tensor:
+        """Unmask an arbitrary contiguous [n_planes, n] digit-plane tensor
         (e.g. this rank's reduce-scattered shard) against matching mask
-        values. u64-order configs only."""
-        if self.wide:
-            raise NotImplementedError("shard unmask covers u64 orders")
+        values. Wide orders take planes of digit_bits-wide digits and [2, n]
+        lo/hi mask values, which may be a column slice mask[:, lo:lo+n]."""
         n = planes.shape[1]
         dt = self.vect_cfg.dtype if dtype is None else dtype
         info = _cfg_scalars(self.unit_cfg)
@@ -233,6 +262,15 @@ class GpuMaskedAggregator:
             raise ZeroDivisionError("scalar_sum is zero")
         vinfo = _cfg_scalars(self.vect_cfg)
         out = torch.empty(n, dtype=self._TORCH_DTYPES[dt], device=planes.device)
+        if self.wide:
+            _check_wide_planes(planes, mask_values)
+            _hip.unmask_u128(
+                planes.data_ptr(), mask_values[0].data_ptr(), mask_values[1].data_ptr(),
+                out.data_ptr(), n, planes.shape[0], self.order, str(vinfo["exp_shift_u64"]),
+                nb_models * vinfo["add_shift"], scalar_sum, dt, digit_bits,
+            )
+            return out
+        _check_u64_digits(digit_bits)
         _hip.unmask(
             planes.data_ptr(), mask_values.data_ptr(), out.data_ptr(), n,
             self.n_digits, self.order, vinfo["exp_shift_u64"],
@@ -343,6 +381,20 @@ class GpuMaskedAggregator:
             return out
         _hip.pack_u64(values.data_ptr(), out.data_ptr(), self.length, self.bpn)
         return out
+
+
+def _check_wide_planes(planes: torch.Tensor, split: torch.Tensor):
+    """The kernels index planes as [k][n] and each lo/hi row as [n]."""
+    if planes.dim() != 2 or not planes.is_contiguous():
+        raise ValueError("planes must be a contiguous [k, n] tensor")
+    if split.dim() != 2 or split.shape[0] != 2 or split.shape[1] != planes.shape[1] \
+            or split.stride(1) != 1:
+        raise ValueError("wide values must be [2, n] lo/hi rows matching the planes")
+
+
+def _check_u64_digits(digit_bits: int):
+    if digit_bits != 32:
+        raise ValueError("u64-order digit planes are 32 bits wide")
 
 
 def _cfg_scalars(cfg):

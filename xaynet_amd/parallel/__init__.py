@@ -12,6 +12,12 @@ the (4x smaller) unmasked output over a full all-reduce. When
 `world * order < 2^64` the reduce-scatter can run on canonical u64 values
 instead of digit planes, halving the bytes on the wire again.
 
+Wide orders (2^64 <= order <= 2^128) carry 3-4 accumulator planes (24-32 B
+per element). Their reduce-scatter re-digitises the locally canonicalised
+value into the fewest digit planes that still leave headroom for the
+cross-rank sum (`compact_digits`): 2 planes up to 120-bit orders, 3 beyond —
+16 or 24 B per element on the wire.
+
 `bench.py` and the multi-GPU serve plane both drive their timed N>1 path
 through this module, so the benchmark measures the production code;
 `tests/test_distributed_planes.py` pins the underlying math on CPU (gloo,
@@ -23,7 +29,26 @@ import os
 
 import torch
 
-__all__ = ["choose_reduce_strategy", "ShardedAggregation"]
+__all__ = ["choose_reduce_strategy", "compact_digits", "ShardedAggregation"]
+
+
+def compact_digits(order_int: int, world: int) -> tuple[int, int]:
+    """Fewest digit planes (k) and their width (w) for a cross-rank sum.
+
+    k is the smallest count with ceil(bits/k) + ceil(log2(world)) <= 63 and
+    w = ceil(bits/k), bits = order_int.bit_length(): every canonical value
+    splits into k digits below 2^w, and a sum of `world` such digits stays
+    below 2^63 (plain int64 collective, no overflow). k == 1 is exactly the
+    "values_rs" condition.
+    """
+    bits = order_int.bit_length()
+    head = max(world - 1, 0).bit_length()  # ceil(log2(world))
+    if head > 62:
+        raise ValueError(f"world {world} leaves no digit headroom in int64")
+    k = 1
+    while -(-bits // k) + head > 63:
+        k += 1
+    return k, -(-bits // k)
 
 
 def choose_reduce_strategy(world: int, length: int, order_int: int,
@@ -37,6 +62,9 @@ def choose_reduce_strategy(world: int, length: int, order_int: int,
                      overflow 63 bits: order_bits + ceil(log2(world)) <= 63.
       "planes_rs"  — reduce-scatter each int64 digit plane, unmask the local
                      shard, all-gather the output.
+      "digits_rs"  — wide orders (>= 2^64): re-digitise the canonical value
+                     into `compact_digits` planes, reduce-scatter those,
+                     unmask the local shard, all-gather the output.
       "all_reduce" — full plane all-reduce (fallback when the length does
                      not shard evenly, or forced with XAYNET_ALLREDUCE=1).
     """
@@ -45,6 +73,8 @@ def choose_reduce_strategy(world: int, length: int, order_int: int,
         return "single"
     if length % world != 0 or env.get("XAYNET_ALLREDUCE", "0") == "1":
         return "all_reduce"
+    if order_int >= 2**64:
+        return "digits_rs"
     if order_int.bit_length() + (world - 1).bit_length() <= 63:
         return "values_rs"
     return "planes_rs"
@@ -60,19 +90,18 @@ class ShardedAggregation:
 
     `mask_total` must be the GLOBAL canonical mask values (same on every
     rank — use `allreduce_mask` to combine per-rank partial mask sums).
-    u64-order configs only (wide orders use the single-GPU staged plane).
+    Wide (u128) orders pass the [2, length] lo/hi split the engine uses.
     """
 
     def __init__(self, eng, dist, rank: int, world: int):
-        if eng.wide and world > 1:
-            raise NotImplementedError("cross-rank sharded aggregation covers u64 "
-                                      "orders; wide (u128) configs run single-GPU")
         self.eng = eng
         self.dist = dist
         self.rank = rank
         self.world = world
         self.strategy = choose_reduce_strategy(world, eng.length, eng.order_int)
         self._shard = eng.length // world if self.strategy.endswith("_rs") else eng.length
+        # wide orders: (plane count, digit width) of the compact cross-rank planes
+        self._digits = compact_digits(eng.order_int, world) if eng.wide else None
         self._buf = {}  # persistent scratch (steady-state rounds reuse them)
 
     def _scratch(self, name: str, *shape, dtype=torch.int64):
@@ -88,11 +117,13 @@ class ShardedAggregation:
         eng = self.eng
         if self.world <= 1:
             return mask_partial
-        planes = self._scratch("mask_planes", eng.n_digits, eng.length)
+        # wide values lift into the same compact planes the digits_rs path uses
+        k, w = self._digits if eng.wide else (eng.n_digits, 32)
+        planes = self._scratch("mask_planes", k, eng.length)
         planes.zero_()
-        eng.values_to_planes(mask_partial, planes)
+        eng.values_to_planes(mask_partial, planes, digit_bits=w)
         self.dist.all_reduce(planes)
-        eng.planes_to_values(planes, mask_partial)
+        eng.planes_to_values(planes, mask_partial, digit_bits=w)
         return mask_partial
 
     def unmask_global(self, mask_total: torch.Tensor, unit_mask_total: int,
@@ -113,6 +144,14 @@ class ShardedAggregation:
             dist.reduce_scatter_tensor(vals_shard, canon)
             out_shard = eng.unmask_values(vals_shard, mask_total[lo:lo + shard],
                                           unit_mask_total, nb_models)
+        elif self.strategy == "digits_rs":
+            k, w = self._digits
+            compact = eng.recode_planes(self._scratch("compact", k, eng.length), w)
+            shard_planes = self._scratch("shard_planes", k, shard)
+            for d in range(k):
+                dist.reduce_scatter_tensor(shard_planes[d], compact[d])
+            out_shard = eng.unmask_planes(shard_planes, mask_total[:, lo:lo + shard],
+                                          unit_mask_total, nb_models, digit_bits=w)
         else:  # planes_rs
             shard_planes = self._scratch("shard_planes", eng.n_digits, shard)
             for d in range(eng.n_digits):
