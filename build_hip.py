@@ -20,8 +20,9 @@ def build(verbose=True):
     ext = sysconfig.get_config_var("EXT_SUFFIX")
     out = os.path.join(root, "xaynet_amd", f"_hip{ext}")
 
-    # skip if up to date
-    if os.path.exists(out) and all(os.path.getmtime(out) > os.path.getmtime(s) for s in src):
+    # skip if up to date (kernels.h: the C ABI both sources include)
+    deps = src + [os.path.join(root, "xaynet_amd", "csrc", "gpu", "kernels.h")]
+    if os.path.exists(out) and all(os.path.getmtime(out) > os.path.getmtime(s) for s in deps):
         if verbose:
             print(f"_hip up to date: {out}")
         return out

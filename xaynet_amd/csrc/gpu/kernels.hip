@@ -26,12 +26,10 @@
 //    prefix-scan compaction assigns the j-th ACCEPTED attempt to element j —
 //    bit-identical to the reference's sequential walk.
 //
-// This file covers group orders < 2^64 (bpn <= 8), which includes every
-// BASELINE.json benchmark config; wider orders currently take the CPU oracle
-// path (multi-digit GPU variants follow the same structure).
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
+// This file covers group orders up to 2^128 (bpn <= 16): orders < 2^64 keep
+// canonical values in one u64, wider ones in split lo/hi u64 planes (the
+// *_u128 kernels). Only Bmax orders beyond 2^128 take the CPU oracle.
+#include "kernels.h"
 
 #define WAVE 64
 
@@ -78,102 +76,49 @@ __device__ void chacha20_block_dev(const uint32_t key[8], uint64_t counter, uint
     out[12] = x12 + s[12]; out[13] = x13 + s[13]; out[14] = x14 + s[14]; out[15] = x15 + s[15];
 }
 
-// Extract draw value: nbytes (<=8) little-endian bytes starting at keystream
-// word `w0` (word-aligned by construction). words[] is a window holding the
-// needed words at index (w0 - window_base).
-__device__ __forceinline__ uint64_t draw_value(const uint32_t* words, int idx, int nbytes) {
-    uint64_t v = uint64_t(words[idx]);
-    if (nbytes > 4) {
-        uint64_t hi = uint64_t(words[idx + 1]);
-        int hb = nbytes - 4;
-        hi &= (hb >= 4) ? 0xffffffffULL : ((1ULL << (8 * hb)) - 1);
-        v |= hi << 32;
-    } else if (nbytes < 4) {
-        v &= (1ULL << (8 * nbytes)) - 1;
+// Block-exclusive scan of one count per thread across NW wavefronts: a
+// wave-level shuffle scan + ONE barrier (the previous 256-thread
+// Hillis-Steele scan cost 16 barriers). Returns the calling thread's
+// exclusive prefix; afterwards wave_tot[w] holds wavefront w's total, so the
+// block total is their sum.
+template <int NW>
+__device__ __forceinline__ uint32_t block_excl_scan(uint32_t mine, uint32_t* wave_tot) {
+    uint32_t lane = threadIdx.x & 63;
+    uint32_t wave = threadIdx.x >> 6;
+    uint32_t incl = mine;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        uint32_t v = __shfl_up(incl, off, 64);
+        if (int(lane) >= off) incl += v;
     }
-    return v;
+    if (lane == 63) wave_tot[wave] = incl;
+    __syncthreads();
+    uint32_t wave_base = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < NW; ++w) {
+        if (w < wave) wave_base += wave_tot[w];
+    }
+    return wave_base + incl - mine;
 }
 
 // --------------------------------------------------- K1a: candidate generate
 //
-// Each thread owns DRAWS_PER_THREAD consecutive draw attempts chosen so a
-// thread's attempts cover whole 16-word ChaCha blocks (no cross-thread
-// sharing): draws_per_thread = 16 / gcd(words_per_draw, 16).
-// Emits candidate values and a per-workgroup accepted count.
-extern "C" __global__ void k1_candidates(
-    const uint32_t* __restrict__ key8,   // 8 words
-    uint64_t start_word,                 // keystream word offset of attempt 0 (after unit draw)
-    uint64_t first_attempt,              // global index of this launch's first attempt
-    uint64_t n_attempts,                 // attempts this launch
-    int words_per_draw, int nbytes, uint64_t order,
-    uint64_t* __restrict__ cand,         // [n_attempts] candidate values
-    uint8_t* __restrict__ accept,        // [n_attempts]
-    uint32_t* __restrict__ wg_counts,    // [gridDim.x] accepted per workgroup
-    int draws_per_thread) {
-    __shared__ uint32_t lds_count;
-    if (threadIdx.x == 0) lds_count = 0;
-    __syncthreads();
-
-    uint32_t key[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) key[i] = key8[i];
-
-    uint64_t t = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    uint64_t a0 = t * draws_per_thread;  // first attempt (relative to launch)
-    int local_accept = 0;
-
-    if (a0 < n_attempts) {
-        // words this thread needs: [w_begin, w_begin + dpt*wpd). For u64
-        // orders wpd <= 2 and dpt*wpd == 16, so <= 2 covering blocks
-        // (start_word may be word-unaligned to a block after the unit draw).
-        uint64_t w_begin = start_word + (first_attempt + a0) * words_per_draw;
-        int total_words = draws_per_thread * words_per_draw;  // == 16
-        uint32_t window[32];
-        uint64_t first_blk = w_begin >> 4;
-        uint64_t last_blk = (w_begin + total_words + 15) >> 4;  // exclusive
-        int cover = int(last_blk - first_blk);                  // 1 or 2
-        uint32_t tmp[16];
-        for (int b = 0; b < cover && b < 2; ++b) {
-            chacha20_block_dev(key, first_blk + b, tmp);
-#pragma unroll
-            for (int i = 0; i < 16; ++i) window[b * 16 + i] = tmp[i];
-        }
-        int base_off = int(w_begin - (first_blk << 4));
-
-        for (int d = 0; d < draws_per_thread; ++d) {
-            uint64_t a = a0 + d;
-            if (a >= n_attempts) break;
-            uint64_t v = draw_value(window, base_off + d * words_per_draw, nbytes);
-            bool ok = v < order;
-            cand[a] = v;
-            accept[a] = ok ? 1 : 0;
-            local_accept += ok ? 1 : 0;
-        }
-    }
-
-    atomicAdd(&lds_count, uint32_t(local_accept));
-    __syncthreads();
-    if (threadIdx.x == 0) wg_counts[blockIdx.x] = lds_count;
-}
-
-// K1a LDS variant: the keystream window of a thread is almost never
-// 16-word-block aligned (the unit draw shifts it), so the register kernel
-// above computes TWO ChaCha blocks per thread to cover its 16 words. Here
-// each thread computes exactly one block into LDS (plus one boundary block
-// per workgroup) and reads its possibly-straddling window from LDS —
-// halving the ChaCha compute, which dominates K1.
+// Each thread owns draws_per_thread consecutive draw attempts chosen so a
+// thread's attempts cover 16 keystream words: draws_per_thread =
+// 16 / words_per_draw. A thread's window is almost never 16-word-block
+// aligned (the unit draw shifts it), so each thread computes exactly one
+// ChaCha block into LDS (plus one boundary block per workgroup) and reads its
+// possibly-straddling window from LDS — half the ChaCha compute, which
+// dominates K1, of generating both covering blocks in registers.
 #define K1_LDS_THREADS 256
 // LDS layout is TRANSPOSED (word-major, stride 257): keystream block b's
 // word i lives at lds[i*257 + b]. Writes (lane = block) and window reads
 // (lane-consecutive blocks, same word index) are then bank-conflict-free —
 // the natural block-major layout had a 47% conflict rate (PMC, r2).
-// The workgroup compaction is a wave-level shuffle scan + one barrier
-// (the previous 256-thread Hillis-Steele scan cost 16 barriers).
 extern "C" __global__ void __launch_bounds__(K1_LDS_THREADS) k1_candidates_lds(
     const uint32_t* __restrict__ key8, uint64_t start_word, uint64_t first_attempt,
     uint64_t n_attempts, int words_per_draw, int nbytes, uint64_t order,
-    uint64_t* __restrict__ cand, uint8_t* __restrict__ accept,
-    uint32_t* __restrict__ wg_counts, int draws_per_thread) {
+    uint64_t* __restrict__ cand, uint32_t* __restrict__ wg_counts, int draws_per_thread) {
     __shared__ uint32_t lds_words[16 * 257];
     __shared__ uint32_t wave_tot[4];
 
@@ -200,9 +145,8 @@ extern "C" __global__ void __launch_bounds__(K1_LDS_THREADS) k1_candidates_lds(
     __syncthreads();
 
     // Accepted draws are compacted IN ORDER into this workgroup's segment of
-    // `cand` (base = wg * 256 * dpt, its worst-case capacity). accept[] is
-    // not written — the scatter pass is a coalesced segment copy.
-    (void)accept;
+    // `cand` (base = wg * 256 * dpt, its worst-case capacity), so the
+    // scatter pass is a coalesced segment copy.
     uint64_t t = uint64_t(blockIdx.x) * K1_LDS_THREADS + threadIdx.x;
     uint64_t a0 = t * draws_per_thread;
     // Accepted draws are recorded as a BITMASK and re-extracted from LDS in
@@ -236,7 +180,9 @@ extern "C" __global__ void __launch_bounds__(K1_LDS_THREADS) k1_candidates_lds(
             }
         }
     }
-    // wave-level exclusive scan of accept counts (one barrier total)
+    // block_excl_scan<4>, written out: calling the helper here changes this
+    // kernel's register allocation (41 -> 40 SGPRs, acceptance loop
+    // rescheduled), and K1's hottest kernel keeps its measured code
     uint32_t lane = threadIdx.x & 63;
     uint32_t wave = threadIdx.x >> 6;
     uint32_t incl = mine;
@@ -333,23 +279,8 @@ extern "C" __global__ void __launch_bounds__(K1_LDS_THREADS) k1_candidates_lds_u
             }
         }
     }
-    // wave-level exclusive scan of accept counts (one barrier total)
-    uint32_t lane = threadIdx.x & 63;
-    uint32_t wave = threadIdx.x >> 6;
-    uint32_t incl = mine;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        uint32_t v = __shfl_up(incl, off, 64);
-        if (int(lane) >= off) incl += v;
-    }
-    if (lane == 63) wave_tot[wave] = incl;
-    __syncthreads();
-    uint32_t wave_base = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < 4; ++w) {
-        if (w < wave) wave_base += wave_tot[w];
-    }
-    uint64_t k = uint64_t(blockIdx.x) * K1_LDS_THREADS * apt + (wave_base + incl - mine);
+    uint64_t k =
+        uint64_t(blockIdx.x) * K1_LDS_THREADS * apt + block_excl_scan<4>(mine, wave_tot);
     while (accept_bits) {
         int d = __builtin_ctz(accept_bits);
         accept_bits &= accept_bits - 1;
@@ -399,133 +330,6 @@ extern "C" __global__ void k1_scatter_compact(
     }
 }
 
-// ---------------------------- K1-fused: single-pass expand (decoupled lookback)
-//
-// Replaces the candidates->scan->scatter 3-pass pipeline: candidate values
-// stay in registers, each block publishes its accepted count to a global
-// state array and resolves its exclusive prefix by looking back over
-// predecessor blocks (rocPRIM/CUB-style decoupled lookback; blocks dispatch
-// in ascending ID on CDNA so progress is guaranteed). Global traffic drops
-// from ~20 B per attempt to 8 B per ACCEPTED draw.
-//
-// state word: [63:62] flag (1 = aggregate, 2 = inclusive), [61:0] count.
-#define K1_FLAG_AGG (1ULL << 62)
-#define K1_FLAG_INC (2ULL << 62)
-#define K1_COUNT_MASK ((1ULL << 62) - 1)
-
-extern "C" __global__ void k1_expand_fused(
-    const uint32_t* __restrict__ key8, uint64_t start_word, uint64_t first_attempt,
-    uint64_t n_attempts, int words_per_draw, int nbytes, uint64_t order,
-    uint64_t out_base, uint64_t* __restrict__ out, uint64_t out_len,
-    unsigned long long* __restrict__ block_state,  // [gridDim.x], zeroed
-    unsigned long long* __restrict__ total,        // [1] launch's accepted count
-    int draws_per_thread) {
-    __shared__ uint32_t lds_scan[256];
-    __shared__ unsigned long long lds_prefix;
-
-    uint32_t key[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) key[i] = key8[i];
-
-    uint64_t t = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    uint64_t a0 = t * draws_per_thread;
-
-    uint64_t vals[16];
-    uint32_t accmask = 0;
-    uint32_t mine = 0;
-    if (a0 < n_attempts) {
-        uint64_t w_begin = start_word + (first_attempt + a0) * words_per_draw;
-        int total_words = draws_per_thread * words_per_draw;  // == 16
-        uint32_t window[32];
-        uint64_t first_blk = w_begin >> 4;
-        uint64_t last_blk = (w_begin + total_words + 15) >> 4;
-        int cover = int(last_blk - first_blk);
-        uint32_t tmp[16];
-        for (int b = 0; b < cover && b < 2; ++b) {
-            chacha20_block_dev(key, first_blk + b, tmp);
-#pragma unroll
-            for (int i = 0; i < 16; ++i) window[b * 16 + i] = tmp[i];
-        }
-        int base_off = int(w_begin - (first_blk << 4));
-#pragma unroll
-        for (int d = 0; d < 16; ++d) {
-            if (d < draws_per_thread && a0 + d < n_attempts) {
-                uint64_t v = draw_value(window, base_off + d * words_per_draw, nbytes);
-                vals[d] = v;
-                if (v < order) {
-                    accmask |= 1u << d;
-                    ++mine;
-                }
-            }
-        }
-    }
-
-    // block-local exclusive offsets
-    lds_scan[threadIdx.x] = mine;
-    __syncthreads();
-    for (uint32_t off = 1; off < blockDim.x; off <<= 1) {
-        uint32_t add = (threadIdx.x >= off) ? lds_scan[threadIdx.x - off] : 0;
-        __syncthreads();
-        lds_scan[threadIdx.x] += add;
-        __syncthreads();
-    }
-    uint32_t block_total = lds_scan[blockDim.x - 1];
-    uint32_t thread_excl = lds_scan[threadIdx.x] - mine;
-
-    // publish aggregate, then resolve the exclusive prefix with a
-    // WAVE-PARALLEL lookback: the first wavefront inspects 64 predecessors
-    // per step (serial per-block walks dominate otherwise)
-    if (threadIdx.x == 0) {
-        __threadfence();
-        atomicExch(&block_state[blockIdx.x], K1_FLAG_AGG | (unsigned long long)block_total);
-    }
-    if (threadIdx.x < WAVE) {
-        int lane = threadIdx.x;
-        unsigned long long prefix = 0;
-        int base = int(blockIdx.x) - 1;  // nearest predecessor (read by lane 0)
-        while (base >= 0) {
-            int j = base - lane;
-            unsigned long long s = K1_FLAG_INC;  // j < 0 contributes 0 with INC
-            if (j >= 0) {
-                s = atomicAdd(&block_state[j], 0ULL);  // global load
-                while ((s >> 62) == 0) {
-                    __builtin_amdgcn_s_sleep(8);  // back off; don't saturate VMEM
-                    s = atomicAdd(&block_state[j], 0ULL);
-                }
-            }
-            bool inc = (s & K1_FLAG_INC) != 0;
-            uint64_t ballot = __ballot(inc);
-            int first_inc = __ffsll((long long)ballot) - 1;  // nearest INC lane
-            unsigned long long contrib =
-                (first_inc < 0 || lane <= first_inc) ? (s & K1_COUNT_MASK) : 0;
-#pragma unroll
-            for (int off = WAVE / 2; off; off >>= 1)
-                contrib += __shfl_down(contrib, off, WAVE);
-            if (lane == 0) prefix += contrib;
-            if (first_inc >= 0) break;
-            base -= WAVE;
-        }
-        if (lane == 0) {
-            __threadfence();
-            atomicExch(&block_state[blockIdx.x],
-                       K1_FLAG_INC | ((prefix + block_total) & K1_COUNT_MASK));
-            lds_prefix = prefix;
-            if (blockIdx.x == gridDim.x - 1) *total = prefix + block_total;
-        }
-    }
-    __syncthreads();
-
-    uint64_t pos = out_base + lds_prefix + thread_excl;
-    uint32_t k = 0;
-#pragma unroll
-    for (int d = 0; d < 16; ++d) {
-        if ((accmask >> d) & 1) {
-            if (pos + k < out_len) out[pos + k] = vals[d];
-            ++k;
-        }
-    }
-}
-
 // --------------------------------------------- K1b: scan of workgroup counts
 // Single-workgroup exclusive scan (counts arrays are small: attempts/(256*dpt)).
 // Hierarchical exclusive scan of the per-workgroup accept counts (used for
@@ -550,23 +354,7 @@ extern "C" __global__ void __launch_bounds__(256) k1_scan_blocks(
         if (base + 2 < n) v2 = counts[base + 2];
         if (base + 3 < n) v3 = counts[base + 3];
     }
-    uint32_t mine = v0 + v1 + v2 + v3;
-    uint32_t lane = threadIdx.x & 63;
-    uint32_t wave = threadIdx.x >> 6;
-    uint32_t incl = mine;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        uint32_t v = __shfl_up(incl, off, 64);
-        if (int(lane) >= off) incl += v;
-    }
-    if (lane == 63) wave_tot[wave] = incl;
-    __syncthreads();
-    uint32_t wave_base = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < 4; ++w) {
-        if (w < wave) wave_base += wave_tot[w];
-    }
-    uint32_t p = wave_base + incl - mine;
+    uint32_t p = block_excl_scan<4>(v0 + v1 + v2 + v3, wave_tot);
     uint32_t o0 = p, o1 = p + v0, o2 = p + v0 + v1, o3 = p + v0 + v1 + v2;
     if (base + 3 < n) {
         *reinterpret_cast<uint4*>(counts + base) = make_uint4(o0, o1, o2, o3);
@@ -613,71 +401,14 @@ extern "C" __global__ void k1_scan(uint32_t* __restrict__ wg_counts, uint32_t n,
     if (e > n) e = n;
     uint32_t sum = 0;
     for (uint32_t i = b; i < e; ++i) sum += wg_counts[i];
-    uint32_t lane = threadIdx.x & 63;
-    uint32_t wave = threadIdx.x >> 6;
-    uint32_t incl = sum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        uint32_t v = __shfl_up(incl, off, 64);
-        if (int(lane) >= off) incl += v;
-    }
-    if (lane == 63) wave_sums[wave] = incl;
-    __syncthreads();
-    uint32_t wave_base = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < 16; ++w) {
-        if (w < wave) wave_base += wave_sums[w];
-    }
-    uint32_t run = wave_base + incl - sum;  // exclusive prefix of this slice
+    uint32_t run = block_excl_scan<16>(sum, wave_sums);  // exclusive prefix of this slice
     for (uint32_t i = b; i < e; ++i) {
         uint32_t v = wg_counts[i];
         wg_counts[i] = run;
         run += v;
     }
-    if (threadIdx.x == T - 1) *total = uint64_t(wave_base) + incl;
-}
-
-// ------------------------------------------------------- K1c: ordered scatter
-extern "C" __global__ void k1_scatter(
-    const uint64_t* __restrict__ cand, const uint8_t* __restrict__ accept,
-    const uint32_t* __restrict__ wg_offsets,  // exclusive offsets per k1 workgroup
-    uint64_t n_attempts, int draws_per_thread,
-    uint64_t out_base,                        // accepted draws before this launch
-    uint64_t* __restrict__ out, uint64_t out_len) {
-    // same geometry as k1_candidates
-    __shared__ uint32_t lds_scan[256];
-    uint64_t t = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    uint64_t a0 = t * draws_per_thread;
-
-    // count of accepted in this thread's attempts
-    uint32_t mine = 0;
-    if (a0 < n_attempts) {
-        for (int d = 0; d < draws_per_thread; ++d) {
-            uint64_t a = a0 + d;
-            if (a >= n_attempts) break;
-            mine += accept[a];
-        }
-    }
-    lds_scan[threadIdx.x] = mine;
-    __syncthreads();
-    for (uint32_t off = 1; off < blockDim.x; off <<= 1) {
-        uint32_t add = (threadIdx.x >= off) ? lds_scan[threadIdx.x - off] : 0;
-        __syncthreads();
-        lds_scan[threadIdx.x] += add;
-        __syncthreads();
-    }
-    uint64_t pos = out_base + wg_offsets[blockIdx.x] + lds_scan[threadIdx.x] - mine;
-
-    if (a0 < n_attempts) {
-        for (int d = 0; d < draws_per_thread; ++d) {
-            uint64_t a = a0 + d;
-            if (a >= n_attempts) break;
-            if (accept[a]) {
-                if (pos < out_len) out[pos] = cand[a];
-                pos += 1;
-            }
-        }
-    }
+    // the last thread's running prefix has passed every count
+    if (threadIdx.x == T - 1) *total = run;
 }
 
 // ------------------------------------------------- K3: batched aggregation
@@ -687,7 +418,7 @@ extern "C" __global__ void k1_scatter(
 // consecutive elements (EPT*bpn % 4 == 0 for aligned u32 loads; updates are
 // 4-byte aligned). Reads each update's bytes once; adds digits into register
 // accumulators; flushes to the planes at the end.
-template <int BPN, int EPT, bool NT = false>
+template <int BPN, int EPT>
 __global__ void k3_aggregate(
     uint64_t* __restrict__ acc,              // [n_digits][len]
     const uint8_t* __restrict__ updates,     // [n_updates][stride]
@@ -721,11 +452,6 @@ __global__ void k3_aggregate(
                 w[4 * i + 2] = v.z;
                 w[4 * i + 3] = v.w;
             }
-        } else if constexpr (NT) {
-            // streaming reads: bypass L2 retention for the 100+ GB update
-            // sweep (each byte is read exactly once per round)
-#pragma unroll
-            for (int i = 0; i < WORDS; ++i) w[i] = __builtin_nontemporal_load(&p[i]);
         } else {
 #pragma unroll
             for (int i = 0; i < WORDS; ++i) w[i] = p[i];
@@ -1248,39 +974,84 @@ extern "C" __global__ void k6_pack_u128(
     for (int b = 8; b < bpn; ++b) p[b] = uint8_t(hi >> (8 * (b - 8)));
 }
 
-// ------------------------------------------------------------ launch helpers
-
-extern "C" {
-
-struct LaunchDims {
-    uint32_t grid, block;
-};
-
-}  // extern C
-
-// host-side dispatch table is in engine.cpp (compiled by hipcc as well)
-
 // ===================================================================
-// Host-side launchers (C ABI consumed by hip_bindings.cpp).
-// All launches go to the null stream, which serializes correctly with
-// PyTorch's default stream on the same device.
+// Host-side launchers (C ABI declared in kernels.h, consumed by
+// hip_bindings.cpp). All launches go to the null stream, which serializes
+// correctly with PyTorch's default stream on the same device.
 
 static inline uint32_t ceil_div_u32(uint64_t a, uint64_t b) { return uint32_t((a + b - 1) / b); }
 
-extern "C" {
+// The "one thread per element, 256 threads" launch: nothing to do for
+// len == 0 (a zero-sized grid is a launch error), else the launch and its
+// error.
+template <typename K, typename... Args>
+static hipError_t launch_1d(K kernel, uint64_t len, Args... args) {
+    if (len == 0) return hipSuccess;
+    kernel<<<dim3(ceil_div_u32(len, 256)), dim3(256), 0, 0>>>(args...);
+    return hipGetLastError();
+}
 
-// XAYNET_K1_REG=1 selects the original all-register 3-pass pipeline
-// (candidates writes cand+accept for every attempt; 2 ChaCha blocks/thread
-// when the stream window is unaligned). Default is the LDS-shared compact
-// pipeline: one ChaCha block per thread, accepted draws written in order
-// to per-workgroup segments, scatter = coalesced segment copy. Both are
-// bit-exact (golden-pinned in tests/test_gpu_kernels.py).
-int xhip_k1_use_reg(void) {
-    static const int use_reg = [] {
-        const char* e = getenv("XAYNET_K1_REG");
-        return (e && e[0] == '1') ? 1 : 0;
-    }();
-    return use_reg;
+// mask::DataType -> element type (+ whether a result truncates toward zero)
+template <typename T, bool TRUNC>
+struct DType {
+    using type = T;
+    static constexpr bool trunc = TRUNC;
+};
+
+// Calls f(DType<..>{}) for dtype 0=f32 1=f64 2=i32 3=i64.
+template <typename F>
+static hipError_t dispatch_dtype(int dtype, F f) {
+    switch (dtype) {
+        case 0: return f(DType<float, false>{});
+        case 1: return f(DType<double, false>{});
+        case 2: return f(DType<int32_t, true>{});
+        case 3: return f(DType<int64_t, true>{});
+        default: return hipErrorInvalidValue;
+    }
+}
+
+// ---- K1: candidates -> scan -> scatter ----
+
+hipError_t xhip_k1_candidates(const uint32_t* key8_dev, uint64_t start_word,
+                              uint64_t first_attempt, uint64_t n_attempts, int words_per_draw,
+                              int nbytes, uint64_t order, uint64_t* cand, uint32_t* wg_counts,
+                              int draws_per_thread, uint32_t* n_wgs_out) {
+    uint32_t wgs = ceil_div_u32(n_attempts, uint64_t(K1_LDS_THREADS) * draws_per_thread);
+    *n_wgs_out = wgs;
+    hipLaunchKernelGGL(k1_candidates_lds, dim3(wgs), dim3(K1_LDS_THREADS), 0, 0, key8_dev,
+                       start_word, first_attempt, n_attempts, words_per_draw, nbytes, order,
+                       cand, wg_counts, draws_per_thread);
+    return hipGetLastError();
+}
+
+hipError_t xhip_k1_candidates_u128(const uint32_t* key8_dev, uint64_t start_word,
+                                   uint64_t first_attempt, uint64_t n_attempts,
+                                   int words_per_draw, int nbytes, uint64_t order_lo,
+                                   uint64_t order_hi, uint64_t* cand_lo, uint64_t* cand_hi,
+                                   uint32_t* wg_counts, int attempts_per_thread,
+                                   uint32_t* n_wgs_out) {
+    uint32_t wgs = ceil_div_u32(n_attempts, uint64_t(K1_LDS_THREADS) * attempts_per_thread);
+    *n_wgs_out = wgs;
+    hipLaunchKernelGGL(k1_candidates_lds_u128, dim3(wgs), dim3(K1_LDS_THREADS), 0, 0, key8_dev,
+                       start_word, first_attempt, n_attempts, words_per_draw, nbytes, order_lo,
+                       order_hi, cand_lo, cand_hi, wg_counts, attempts_per_thread);
+    return hipGetLastError();
+}
+
+// Exclusive scan of the per-workgroup accept counts + their total. Up to
+// 2048 counts: the single-workgroup kernel. Beyond: coalesced tile scan +
+// tiny middle scan over the tile totals + base add.
+hipError_t xhip_k1_scan_hier(uint32_t* wg_counts, uint32_t n, uint32_t* blk_tmp,
+                             uint64_t* total_dev) {
+    if (n <= 2048) {
+        hipLaunchKernelGGL(k1_scan, dim3(1), dim3(1024), 0, 0, wg_counts, n, total_dev);
+        return hipGetLastError();
+    }
+    uint32_t nblk = (n + 1023) / 1024;
+    hipLaunchKernelGGL(k1_scan_blocks, dim3(nblk), dim3(256), 0, 0, wg_counts, n, blk_tmp);
+    hipLaunchKernelGGL(k1_scan, dim3(1), dim3(1024), 0, 0, blk_tmp, nblk, total_dev);
+    hipLaunchKernelGGL(k1_scan_addbase, dim3(nblk), dim3(256), 0, 0, wg_counts, n, blk_tmp);
+    return hipGetLastError();
 }
 
 hipError_t xhip_k1_scatter_compact(const uint64_t* cand, const uint32_t* wg_offsets,
@@ -1292,72 +1063,18 @@ hipError_t xhip_k1_scatter_compact(const uint64_t* cand, const uint32_t* wg_offs
     return hipGetLastError();
 }
 
-hipError_t xhip_k1_candidates(const uint32_t* key8_dev, uint64_t start_word,
-                              uint64_t first_attempt, uint64_t n_attempts, int words_per_draw,
-                              int nbytes, uint64_t order, uint64_t* cand, uint8_t* accept,
-                              uint32_t* wg_counts, int draws_per_thread, uint32_t* n_wgs_out) {
-    uint32_t threads = 256;
-    uint64_t per_wg = uint64_t(threads) * draws_per_thread;
-    uint32_t wgs = ceil_div_u32(n_attempts, per_wg);
-    *n_wgs_out = wgs;
-    if (xhip_k1_use_reg())
-        hipLaunchKernelGGL(k1_candidates, dim3(wgs), dim3(threads), 0, 0, key8_dev, start_word,
-                           first_attempt, n_attempts, words_per_draw, nbytes, order, cand,
-                           accept, wg_counts, draws_per_thread);
-    else
-        hipLaunchKernelGGL(k1_candidates_lds, dim3(wgs), dim3(threads), 0, 0, key8_dev,
-                           start_word, first_attempt, n_attempts, words_per_draw, nbytes, order,
-                           cand, accept, wg_counts, draws_per_thread);
+hipError_t xhip_k1_scatter_compact_u128(const uint64_t* cand_lo, const uint64_t* cand_hi,
+                                        const uint32_t* wg_offsets, const uint64_t* total_dev,
+                                        uint32_t n_wgs, int apt, uint64_t out_base,
+                                        uint64_t* out_lo, uint64_t* out_hi, uint64_t out_len) {
+    if (n_wgs == 0) return hipSuccess;
+    hipLaunchKernelGGL(k1_scatter_compact_u128, dim3(n_wgs), dim3(256), 0, 0, cand_lo, cand_hi,
+                       wg_offsets, total_dev, n_wgs, 256 * apt, out_base, out_lo, out_hi,
+                       out_len);
     return hipGetLastError();
 }
 
-hipError_t xhip_k1_scan(uint32_t* wg_counts, uint32_t n, uint64_t* total_dev) {
-    hipLaunchKernelGGL(k1_scan, dim3(1), dim3(1024), 0, 0, wg_counts, n, total_dev);
-    return hipGetLastError();
-}
-
-// Hierarchical scan: coalesced tile scan + tiny middle scan + base add.
-// blk_tmp must hold ceil(n/1024) u32. Falls back to the single-WG kernel
-// for small n (or when no scratch is provided).
-hipError_t xhip_k1_scan_hier(uint32_t* wg_counts, uint32_t n, uint32_t* blk_tmp,
-                             uint64_t* total_dev) {
-    if (n <= 2048 || blk_tmp == nullptr)
-        return xhip_k1_scan(wg_counts, n, total_dev);
-    uint32_t nblk = (n + 1023) / 1024;
-    hipLaunchKernelGGL(k1_scan_blocks, dim3(nblk), dim3(256), 0, 0, wg_counts, n, blk_tmp);
-    hipLaunchKernelGGL(k1_scan, dim3(1), dim3(1024), 0, 0, blk_tmp, nblk, total_dev);
-    hipLaunchKernelGGL(k1_scan_addbase, dim3(nblk), dim3(256), 0, 0, wg_counts, n, blk_tmp);
-    return hipGetLastError();
-}
-
-hipError_t xhip_k1_scatter(const uint64_t* cand, const uint8_t* accept,
-                           const uint32_t* wg_offsets, uint64_t n_attempts, int draws_per_thread,
-                           uint64_t out_base, uint64_t* out, uint64_t out_len) {
-    uint32_t threads = 256;
-    uint64_t per_wg = uint64_t(threads) * draws_per_thread;
-    uint32_t wgs = ceil_div_u32(n_attempts, per_wg);
-    hipLaunchKernelGGL(k1_scatter, dim3(wgs), dim3(threads), 0, 0, cand, accept, wg_offsets,
-                       n_attempts, draws_per_thread, out_base, out, out_len);
-    return hipGetLastError();
-}
-
-hipError_t xhip_k1_expand_fused(const uint32_t* key8, uint64_t start_word,
-                                uint64_t first_attempt, uint64_t n_attempts, int words_per_draw,
-                                int nbytes, uint64_t order, uint64_t out_base, uint64_t* out,
-                                uint64_t out_len, unsigned long long* block_state,
-                                unsigned long long* total, int draws_per_thread,
-                                uint32_t* n_wgs_out) {
-    uint32_t threads = 256;
-    uint64_t per_wg = uint64_t(threads) * draws_per_thread;
-    uint32_t wgs = ceil_div_u32(n_attempts, per_wg);
-    *n_wgs_out = wgs;
-    hipError_t e = hipMemsetAsync(block_state, 0, sizeof(unsigned long long) * wgs, 0);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k1_expand_fused, dim3(wgs), dim3(threads), 0, 0, key8, start_word,
-                       first_attempt, n_attempts, words_per_draw, nbytes, order, out_base, out,
-                       out_len, block_state, total, draws_per_thread);
-    return hipGetLastError();
-}
+// ---- K3 ----
 
 hipError_t xhip_k3_aggregate(uint64_t* acc, const uint8_t* updates, uint64_t stride,
                              uint32_t n_updates, uint64_t len, int bpn, int ept) {
@@ -1380,20 +1097,6 @@ hipError_t xhip_k3_aggregate(uint64_t* acc, const uint8_t* updates, uint64_t str
         else                                                                                    \
             K3_LAUNCH(BPN, DEFEPT)                                                              \
         break;
-    // ept=104: nontemporal-load variant of the default (EPT=4) kernel
-    if (ept == 104 && bpn == 7) {
-        uint32_t wgs = ceil_div_u32((len + 3) / 4, threads);
-        hipLaunchKernelGGL((k3_aggregate<7, 4, true>), dim3(wgs), dim3(threads), 0, 0, acc,
-                           updates, stride, n_updates, len);
-        return hipGetLastError();
-    }
-    // ept=304: 512-thread blocks at EPT=4 (latency-hiding shape experiment)
-    if (ept == 304 && bpn == 7) {
-        uint32_t wgs = ceil_div_u32((len + 3) / 4, 512);
-        hipLaunchKernelGGL((k3_aggregate<7, 4>), dim3(wgs), dim3(512), 0, 0, acc, updates,
-                           stride, n_updates, len);
-        return hipGetLastError();
-    }
     // ept=201/202: LDS-staged variant with E=2048/4096-element tiles (16B-
     // aligned rows required; alignment is guaranteed by the pool allocator)
     if (ept == 201 || ept == 202) {
@@ -1454,246 +1157,136 @@ hipError_t xhip_k3_aggregate(uint64_t* acc, const uint8_t* updates, uint64_t str
     return hipGetLastError();
 }
 
+// ---- K2/K4/K5/K6, u64 orders ----
+
+hipError_t xhip_k4_unmask(const uint64_t* acc, const uint64_t* mask, int dtype, void* out,
+                          uint64_t len, int n_digits, uint64_t order, uint64_t exp_shift,
+                          double n_add_shift, double scalar_sum) {
+    return dispatch_dtype(dtype, [&](auto t) {
+        using OUT = typename decltype(t)::type;
+        return launch_1d(k4_unmask<OUT, decltype(t)::trunc>, len, acc, mask,
+                         static_cast<OUT*>(out), len, n_digits, order, exp_shift, n_add_shift,
+                         scalar_sum);
+    });
+}
+
+hipError_t xhip_k4_unmask_values(const uint64_t* vals, const uint64_t* mask, int dtype,
+                                 void* out, uint64_t len, uint64_t order, uint64_t exp_shift,
+                                 double n_add_shift, double scalar_sum) {
+    return dispatch_dtype(dtype, [&](auto t) {
+        using OUT = typename decltype(t)::type;
+        return launch_1d(k4_unmask_values<OUT, decltype(t)::trunc>, len, vals, mask,
+                         static_cast<OUT*>(out), len, order, exp_shift, n_add_shift,
+                         scalar_sum);
+    });
+}
+
+hipError_t xhip_k2_canonicalize(const uint64_t* acc, uint64_t* out, uint64_t len, int n_digits,
+                                uint64_t order) {
+    return launch_1d(k2_canonicalize, len, acc, out, len, n_digits, order);
+}
+
+hipError_t xhip_k2_mod_add_u64(uint64_t* a, const uint64_t* b, uint64_t len, uint64_t order) {
+    return launch_1d(k2_mod_add_u64, len, a, b, len, order);
+}
+
+hipError_t xhip_k5_mask_pack(const uint64_t* mask, uint8_t* out, uint64_t len, int bpn,
+                             uint64_t order, uint64_t participant, double scalar,
+                             double add_shift, double exp_shift_d, uint64_t exp_shift) {
+    return launch_1d(k5_mask_pack, len, mask, out, len, bpn, order, participant, scalar,
+                     add_shift, exp_shift_d, exp_shift);
+}
+
+hipError_t xhip_k6_unpack_u64(const uint8_t* in, uint64_t* out, uint64_t len, int bpn) {
+    return launch_1d(k6_unpack_u64, len, in, out, len, bpn);
+}
+
+hipError_t xhip_k6_pack_u64(const uint64_t* in, uint8_t* out, uint64_t len, int bpn) {
+    return launch_1d(k6_pack_u64, len, in, out, len, bpn);
+}
+
+hipError_t xhip_add_u64_to_planes(uint64_t* acc, const uint64_t* vals, uint64_t len,
+                                  int n_digits) {
+    return launch_1d(k_add_u64_to_planes, len, acc, vals, len, n_digits);
+}
+
+// ---- K2/K4/K5/K6, u128 orders ----
 // digit_bits 32 (the accumulator layout) takes the compile-time variant; any
 // other width in 1..63 the runtime-shift one.
+
 hipError_t xhip_k2_canonicalize_u128(const uint64_t* acc, uint64_t* out_lo, uint64_t* out_hi,
                                      uint64_t len, int n_digits, int digit_bits,
                                      uint64_t order_lo, uint64_t order_hi) {
     if (digit_bits < 1 || digit_bits > 63 || n_digits < 1) return hipErrorInvalidValue;
-    if (len == 0) return hipSuccess;
-    uint32_t threads = 256, wgs = ceil_div_u32(len, threads);
-    if (digit_bits == 32)
-        hipLaunchKernelGGL((k2_canonicalize_u128<32>), dim3(wgs), dim3(threads), 0, 0, acc,
-                           out_lo, out_hi, len, n_digits, digit_bits, order_lo, order_hi);
-    else
-        hipLaunchKernelGGL((k2_canonicalize_u128<0>), dim3(wgs), dim3(threads), 0, 0, acc,
-                           out_lo, out_hi, len, n_digits, digit_bits, order_lo, order_hi);
-    return hipGetLastError();
+    return launch_1d(digit_bits == 32 ? k2_canonicalize_u128<32> : k2_canonicalize_u128<0>, len,
+                     acc, out_lo, out_hi, len, n_digits, digit_bits, order_lo, order_hi);
 }
 
 hipError_t xhip_add_u128_to_planes(uint64_t* planes, const uint64_t* lo, const uint64_t* hi,
                                    uint64_t len, int k, int digit_bits) {
     if (digit_bits < 1 || digit_bits > 63 || k < 1) return hipErrorInvalidValue;
-    if (len == 0) return hipSuccess;
-    uint32_t threads = 256, wgs = ceil_div_u32(len, threads);
-    hipLaunchKernelGGL(k_add_u128_to_planes, dim3(wgs), dim3(threads), 0, 0, planes, lo, hi, len,
-                       k, digit_bits);
-    return hipGetLastError();
+    return launch_1d(k_add_u128_to_planes, len, planes, lo, hi, len, k, digit_bits);
 }
 
 hipError_t xhip_k2_recode_planes_u128(const uint64_t* acc, uint64_t* out, uint64_t len,
                                       int n_digits, uint64_t order_lo, uint64_t order_hi, int k,
                                       int digit_bits) {
     if (digit_bits < 1 || digit_bits > 63 || k < 1 || n_digits < 1) return hipErrorInvalidValue;
-    if (len == 0) return hipSuccess;
-    uint32_t threads = 256, wgs = ceil_div_u32(len, threads);
-    hipLaunchKernelGGL(k2_recode_planes_u128, dim3(wgs), dim3(threads), 0, 0, acc, out, len,
-                       n_digits, order_lo, order_hi, k, digit_bits);
-    return hipGetLastError();
+    return launch_1d(k2_recode_planes_u128, len, acc, out, len, n_digits, order_lo, order_hi, k,
+                     digit_bits);
 }
 
 hipError_t xhip_k2_mod_add_u128(uint64_t* a_lo, uint64_t* a_hi, const uint64_t* b_lo,
                                 const uint64_t* b_hi, uint64_t len, uint64_t order_lo,
                                 uint64_t order_hi) {
-    uint32_t threads = 256, wgs = ceil_div_u32(len, threads);
-    hipLaunchKernelGGL(k2_mod_add_u128, dim3(wgs), dim3(threads), 0, 0, a_lo, a_hi, b_lo, b_hi,
-                       len, order_lo, order_hi);
-    return hipGetLastError();
+    return launch_1d(k2_mod_add_u128, len, a_lo, a_hi, b_lo, b_hi, len, order_lo, order_hi);
 }
 
 hipError_t xhip_k6_unpack_u128(const uint8_t* in, uint64_t* out_lo, uint64_t* out_hi,
                                uint64_t len, int bpn) {
-    uint32_t threads = 256, wgs = ceil_div_u32(len, threads);
-    hipLaunchKernelGGL(k6_unpack_u128, dim3(wgs), dim3(threads), 0, 0, in, out_lo, out_hi, len,
-                       bpn);
-    return hipGetLastError();
+    return launch_1d(k6_unpack_u128, len, in, out_lo, out_hi, len, bpn);
 }
 
-// wide K4 launcher: dtype 0=f32 1=f64 2=i32 3=i64 (integers truncate);
-// digit_bits 32 takes the compile-time variant, as above
+hipError_t xhip_k6_pack_u128(const uint64_t* in_lo, const uint64_t* in_hi, uint8_t* out,
+                             uint64_t len, int bpn) {
+    return launch_1d(k6_pack_u128, len, in_lo, in_hi, out, len, bpn);
+}
+
 hipError_t xhip_k4_unmask_u128(const uint64_t* acc, const uint64_t* mask_lo,
                                const uint64_t* mask_hi, void* out, uint64_t len, int n_digits,
                                int digit_bits, uint64_t order_lo, uint64_t order_hi,
                                uint64_t exp_lo, uint64_t exp_hi, double n_add_shift,
                                double scalar_sum, int dtype) {
     if (digit_bits < 1 || digit_bits > 63 || n_digits < 1) return hipErrorInvalidValue;
-    if (len == 0) return hipSuccess;
-    uint32_t threads = 256, wgs = ceil_div_u32(len, threads);
-#define K4W(OUT, TRUNC, DB)                                                                  \
-    hipLaunchKernelGGL((k4_unmask_u128<OUT, TRUNC, DB>), dim3(wgs), dim3(threads), 0, 0, acc, \
-                       mask_lo, mask_hi, reinterpret_cast<OUT*>(out), len, n_digits,         \
-                       digit_bits, order_lo, order_hi, exp_lo, exp_hi, n_add_shift,          \
-                       scalar_sum)
-    if (digit_bits == 32) {
-        switch (dtype) {
-            case 0: K4W(float, false, 32); break;
-            case 1: K4W(double, false, 32); break;
-            case 2: K4W(int32_t, true, 32); break;
-            case 3: K4W(int64_t, true, 32); break;
-            default: return hipErrorInvalidValue;
-        }
-    } else {
-        switch (dtype) {
-            case 0: K4W(float, false, 0); break;
-            case 1: K4W(double, false, 0); break;
-            case 2: K4W(int32_t, true, 0); break;
-            case 3: K4W(int64_t, true, 0); break;
-            default: return hipErrorInvalidValue;
-        }
-    }
-#undef K4W
-    return hipGetLastError();
-}
-
-#define K4_LAUNCHER(NAME, OUT, TRUNC)                                                            \
-    hipError_t NAME(const uint64_t* acc, const uint64_t* mask, OUT* out, uint64_t len,           \
-                    int n_digits, uint64_t order, uint64_t exp_shift, double n_add_shift,        \
-                    double scalar_sum) {                                                     \
-        uint32_t threads = 256, wgs = ceil_div_u32(len, threads);                                \
-        hipLaunchKernelGGL((k4_unmask<OUT, TRUNC>), dim3(wgs), dim3(threads), 0, 0, acc, mask,   \
-                           out, len, n_digits, order, exp_shift, n_add_shift, scalar_sum);   \
-        return hipGetLastError();                                                                \
-    }
-K4_LAUNCHER(xhip_k4_unmask_f32, float, false)
-K4_LAUNCHER(xhip_k4_unmask_f64, double, false)
-K4_LAUNCHER(xhip_k4_unmask_i32, int32_t, true)
-K4_LAUNCHER(xhip_k4_unmask_i64, int64_t, true)
-#undef K4_LAUNCHER
-
-#define K4V_LAUNCHER(NAME, OUT, TRUNC)                                                           \
-    hipError_t NAME(const uint64_t* vals, const uint64_t* mask, OUT* out, uint64_t len,          \
-                    uint64_t order, uint64_t exp_shift, double n_add_shift,                      \
-                    double scalar_sum) {                                                     \
-        uint32_t threads = 256, wgs = ceil_div_u32(len, threads);                                \
-        hipLaunchKernelGGL((k4_unmask_values<OUT, TRUNC>), dim3(wgs), dim3(threads), 0, 0,       \
-                           vals, mask, out, len, order, exp_shift, n_add_shift, scalar_sum); \
-        return hipGetLastError();                                                                \
-    }
-K4V_LAUNCHER(xhip_k4_unmask_values_f32, float, false)
-K4V_LAUNCHER(xhip_k4_unmask_values_f64, double, false)
-K4V_LAUNCHER(xhip_k4_unmask_values_i32, int32_t, true)
-K4V_LAUNCHER(xhip_k4_unmask_values_i64, int64_t, true)
-#undef K4V_LAUNCHER
-
-hipError_t xhip_k2_canonicalize(const uint64_t* acc, uint64_t* out, uint64_t len, int n_digits,
-                                uint64_t order) {
-    uint32_t threads = 256, wgs = ceil_div_u32(len, threads);
-    hipLaunchKernelGGL(k2_canonicalize, dim3(wgs), dim3(threads), 0, 0, acc, out, len, n_digits,
-                       order);
-    return hipGetLastError();
-}
-
-hipError_t xhip_k2_mod_add_u64(uint64_t* a, const uint64_t* b, uint64_t len, uint64_t order) {
-    uint32_t threads = 256, wgs = ceil_div_u32(len, threads);
-    hipLaunchKernelGGL(k2_mod_add_u64, dim3(wgs), dim3(threads), 0, 0, a, b, len, order);
-    return hipGetLastError();
-}
-
-hipError_t xhip_k5_mask_pack(const uint64_t* mask, uint8_t* out, uint64_t len, int bpn,
-                             uint64_t order, uint64_t participant, double scalar, double add_shift,
-                             double exp_shift_d, uint64_t exp_shift) {
-    uint32_t threads = 256, wgs = ceil_div_u32(len, threads);
-    hipLaunchKernelGGL(k5_mask_pack, dim3(wgs), dim3(threads), 0, 0, mask, out, len, bpn, order,
-                       participant, scalar, add_shift, exp_shift_d, exp_shift);
-    return hipGetLastError();
-}
-
-hipError_t xhip_k6_unpack_u64(const uint8_t* in, uint64_t* out, uint64_t len, int bpn) {
-    uint32_t threads = 256, wgs = ceil_div_u32(len, threads);
-    hipLaunchKernelGGL(k6_unpack_u64, dim3(wgs), dim3(threads), 0, 0, in, out, len, bpn);
-    return hipGetLastError();
-}
-
-hipError_t xhip_k6_pack_u64(const uint64_t* in, uint8_t* out, uint64_t len, int bpn) {
-    uint32_t threads = 256, wgs = ceil_div_u32(len, threads);
-    hipLaunchKernelGGL(k6_pack_u64, dim3(wgs), dim3(threads), 0, 0, in, out, len, bpn);
-    return hipGetLastError();
-}
-
-hipError_t xhip_add_u64_to_planes(uint64_t* acc, const uint64_t* vals, uint64_t len,
-                                  int n_digits) {
-    uint32_t threads = 256, wgs = ceil_div_u32(len, threads);
-    hipLaunchKernelGGL(k_add_u64_to_planes, dim3(wgs), dim3(threads), 0, 0, acc, vals, len,
-                       n_digits);
-    return hipGetLastError();
-}
-
-// ---- wide (u128-order) K1/K5/K6 launchers ----
-
-hipError_t xhip_k1_candidates_u128(const uint32_t* key8_dev, uint64_t start_word,
-                                   uint64_t first_attempt, uint64_t n_attempts,
-                                   int words_per_draw, int nbytes, uint64_t order_lo,
-                                   uint64_t order_hi, uint64_t* cand_lo, uint64_t* cand_hi,
-                                   uint32_t* wg_counts, int attempts_per_thread,
-                                   uint32_t* n_wgs_out) {
-    uint64_t per_wg = uint64_t(256) * attempts_per_thread;
-    uint32_t wgs = ceil_div_u32(n_attempts, per_wg);
-    *n_wgs_out = wgs;
-    hipLaunchKernelGGL(k1_candidates_lds_u128, dim3(wgs), dim3(256), 0, 0, key8_dev, start_word,
-                       first_attempt, n_attempts, words_per_draw, nbytes, order_lo, order_hi,
-                       cand_lo, cand_hi, wg_counts, attempts_per_thread);
-    return hipGetLastError();
-}
-
-hipError_t xhip_k1_scatter_compact_u128(const uint64_t* cand_lo, const uint64_t* cand_hi,
-                                        const uint32_t* wg_offsets, const uint64_t* total_dev,
-                                        uint32_t n_wgs, int apt, uint64_t out_base,
-                                        uint64_t* out_lo, uint64_t* out_hi, uint64_t out_len) {
-    if (n_wgs == 0) return hipSuccess;
-    hipLaunchKernelGGL(k1_scatter_compact_u128, dim3(n_wgs), dim3(256), 0, 0, cand_lo, cand_hi,
-                       wg_offsets, total_dev, n_wgs, 256 * apt, out_base, out_lo, out_hi,
-                       out_len);
-    return hipGetLastError();
+    return dispatch_dtype(dtype, [&](auto t) {
+        using OUT = typename decltype(t)::type;
+        constexpr bool TRUNC = decltype(t)::trunc;
+        return launch_1d(digit_bits == 32 ? k4_unmask_u128<OUT, TRUNC, 32>
+                                          : k4_unmask_u128<OUT, TRUNC, 0>,
+                         len, acc, mask_lo, mask_hi, static_cast<OUT*>(out), len, n_digits,
+                         digit_bits, order_lo, order_hi, exp_lo, exp_hi, n_add_shift,
+                         scalar_sum);
+    });
 }
 
 hipError_t xhip_k5_mask_pack_u128(const uint64_t* mask_lo, const uint64_t* mask_hi, uint8_t* out,
                                   uint64_t len, int bpn, uint64_t order_lo, uint64_t order_hi,
                                   uint64_t participant, double scalar, double add_shift,
                                   double exp_shift_d) {
-    uint32_t threads = 256, wgs = ceil_div_u32(len, threads);
-    hipLaunchKernelGGL(k5_mask_pack_u128, dim3(wgs), dim3(threads), 0, 0, mask_lo, mask_hi, out,
-                       len, bpn, order_lo, order_hi, participant, scalar, add_shift,
-                       exp_shift_d);
-    return hipGetLastError();
+    return launch_1d(k5_mask_pack_u128, len, mask_lo, mask_hi, out, len, bpn, order_lo, order_hi,
+                     participant, scalar, add_shift, exp_shift_d);
 }
 
-hipError_t xhip_k6_pack_u128(const uint64_t* in_lo, const uint64_t* in_hi, uint8_t* out,
-                             uint64_t len, int bpn) {
-    uint32_t threads = 256, wgs = ceil_div_u32(len, threads);
-    hipLaunchKernelGGL(k6_pack_u128, dim3(wgs), dim3(threads), 0, 0, in_lo, in_hi, out, len,
-                       bpn);
-    return hipGetLastError();
-}
+// ---- K5w ----
 
-// K5w launcher: dtype 0=f32 1=f64 2=i32 3=i64; wide = order > 2^64
 hipError_t xhip_k5_mask_weights(const void* w, int dtype, const uint64_t* mask_lo,
                                 const uint64_t* mask_hi, uint8_t* out, uint64_t len, int bpn,
                                 uint64_t order_lo, uint64_t order_hi, double scalar,
                                 double add_shift, uint64_t exp_lo, uint64_t exp_hi, int wide) {
-    uint32_t threads = 256, wgs = ceil_div_u32(len, threads);
-#define K5W(T, W)                                                                          \
-    hipLaunchKernelGGL((k5_mask_weights<T, W>), dim3(wgs), dim3(threads), 0, 0,            \
-                       reinterpret_cast<const T*>(w), mask_lo, mask_hi, out, len, bpn,     \
-                       order_lo, order_hi, scalar, add_shift, exp_lo, exp_hi)
-    if (wide) {
-        switch (dtype) {
-            case 0: K5W(float, true); break;
-            case 1: K5W(double, true); break;
-            case 2: K5W(int32_t, true); break;
-            case 3: K5W(int64_t, true); break;
-            default: return hipErrorInvalidValue;
-        }
-    } else {
-        switch (dtype) {
-            case 0: K5W(float, false); break;
-            case 1: K5W(double, false); break;
-            case 2: K5W(int32_t, false); break;
-            case 3: K5W(int64_t, false); break;
-            default: return hipErrorInvalidValue;
-        }
-    }
-#undef K5W
-    return hipGetLastError();
+    return dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        return launch_1d(wide ? k5_mask_weights<T, true> : k5_mask_weights<T, false>, len,
+                         static_cast<const T*>(w), mask_lo, mask_hi, out, len, bpn, order_lo,
+                         order_hi, scalar, add_shift, exp_lo, exp_hi);
+    });
 }
-
-}  // extern "C"

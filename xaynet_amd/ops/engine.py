@@ -192,20 +192,25 @@ class GpuMaskedAggregator:
 
     _TORCH_DTYPES = {0: torch.float32, 1: torch.float64, 2: torch.int32, 3: torch.int64}
 
+    def _unmask_scalars(self, mask_unit: int, nb: int, dtype: int | None = None):
+        """What every unmask needs besides the tensors: scalar_sum =
+        n1/exp_1 - nb*add_1 (exact on CPU), the vect config's shifts, and the
+        output mask::DataType (default: the vect config's)."""
+        info = _cfg_scalars(self.unit_cfg)
+        n1 = (self.unit_acc + int(self.unit_cfg.order) - mask_unit) % int(self.unit_cfg.order)
+        scalar_sum = n1 / info["exp_shift"] - nb * info["add_shift"]
+        if scalar_sum == 0:
+            raise ZeroDivisionError("scalar_sum is zero")
+        dt = self.vect_cfg.dtype if dtype is None else dtype
+        return scalar_sum, _cfg_scalars(self.vect_cfg), dt
+
     def unmask(self, mask_values: torch.Tensor, mask_unit: int,
                nb_models: int | None = None, dtype: int | None = None) -> torch.Tensor:
         """Unmask the aggregate into model weights (reference unmask math,
         masking.rs:190-231). dtype follows mask::DataType (default: the vect
         config's data type); integers truncate toward zero."""
         nb = self.nb_models if nb_models is None else nb_models
-        dt = self.vect_cfg.dtype if dtype is None else dtype
-        info = _cfg_scalars(self.unit_cfg)
-        # scalar_sum = n1/exp_1 - nb*add_1 (exact on CPU)
-        n1 = (self.unit_acc + int(self.unit_cfg.order) - mask_unit) % int(self.unit_cfg.order)
-        scalar_sum = n1 / info["exp_shift"] - nb * info["add_shift"]
-        if scalar_sum == 0:
-            raise ZeroDivisionError("scalar_sum is zero")
-        vinfo = _cfg_scalars(self.vect_cfg)
+        scalar_sum, vinfo, dt = self._unmask_scalars(mask_unit, nb, dtype)
         out = torch.empty(self.length, dtype=self._TORCH_DTYPES[dt], device=self.device)
         if self.wide:
             _hip.unmask_u128(
@@ -232,13 +237,7 @@ class GpuMaskedAggregator:
         if self.wide:
             raise NotImplementedError("values unmask covers u64 orders")
         n = vals.numel()
-        dt = self.vect_cfg.dtype if dtype is None else dtype
-        info = _cfg_scalars(self.unit_cfg)
-        n1 = (self.unit_acc + int(self.unit_cfg.order) - mask_unit) % int(self.unit_cfg.order)
-        scalar_sum = n1 / info["exp_shift"] - nb_models * info["add_shift"]
-        if scalar_sum == 0:
-            raise ZeroDivisionError("scalar_sum is zero")
-        vinfo = _cfg_scalars(self.vect_cfg)
+        scalar_sum, vinfo, dt = self._unmask_scalars(mask_unit, nb_models, dtype)
         out = torch.empty(n, dtype=self._TORCH_DTYPES[dt], device=vals.device)
         _hip.unmask_values(
             vals.data_ptr(), mask_values.data_ptr(), out.data_ptr(), n, self.order,
@@ -254,13 +253,7 @@ class GpuMaskedAggregator:
         values. Wide orders take planes of digit_bits-wide digits and [2, n]
         lo/hi mask values, which may be a column slice mask[:, lo:lo+n]."""
         n = planes.shape[1]
-        dt = self.vect_cfg.dtype if dtype is None else dtype
-        info = _cfg_scalars(self.unit_cfg)
-        n1 = (self.unit_acc + int(self.unit_cfg.order) - mask_unit) % int(self.unit_cfg.order)
-        scalar_sum = n1 / info["exp_shift"] - nb_models * info["add_shift"]
-        if scalar_sum == 0:
-            raise ZeroDivisionError("scalar_sum is zero")
-        vinfo = _cfg_scalars(self.vect_cfg)
+        scalar_sum, vinfo, dt = self._unmask_scalars(mask_unit, nb_models, dtype)
         out = torch.empty(n, dtype=self._TORCH_DTYPES[dt], device=planes.device)
         if self.wide:
             _check_wide_planes(planes, mask_values)
