@@ -30,8 +30,7 @@ for name, args in [("u64 f32-m6 (bpn7)", (1, 0, 0, 6)),
                    ("wide f64-b4-m9 (bpn14, 4w/draw)", (1, 1, 4, 9))]:
     c = mk.MaskConfig(*args)
     eng = GpuMaskedAggregator(c, c, N)
-    shape = (2, N) if eng.wide else (N,)
-    out = torch.empty(*shape, dtype=torch.int64, device="cuda")
+    out = eng.new_values()
     seed = b"\x05" * 32
     dt = timed(lambda: eng.derive_mask_values(seed, out=out))
     print(f"K1 {name}: {dt*1e3:.2f} ms/mask ({N/dt/1e6:.1f} Melt/s)")
@@ -42,15 +41,14 @@ for name, args in [("u64 f32-m6 (bpn7)", (1, 0, 0, 6)),
     # breakdown: derive (K1) vs quantize+mask+pack kernel vs D2H assembly
     mv = eng.derive_mask_values(seed)
     from xaynet_amd import _hip
-    from xaynet_amd.ops.engine import _cfg_scalars
+    from xaynet_amd.ops.base import _cfg_scalars
     vinfo = _cfg_scalars(c)
     outb = torch.empty(N * eng.bpn, dtype=torch.uint8, device="cuda")
-    lo = mv[0].data_ptr() if eng.wide else mv.data_ptr()
-    hi = mv[1].data_ptr() if eng.wide else mv.data_ptr()
+    lo, hi, _ = eng._vals(mv)
     dt_map = {torch.float32: 0, torch.float64: 1}
     dk = timed(lambda: _hip.mask_weights(
         w.data_ptr(), dt_map[w.dtype], lo, hi, outb.data_ptr(), N, eng.bpn,
-        eng.order, 0.1, vinfo["add_shift"], str(vinfo["exp_shift_u64"]), eng.wide))
+        eng.order, 0.1, vinfo["add_shift"], str(vinfo["exp_shift_u64"])))
     print(f"  K5w kernel alone: {dk*1e3:.2f} ms")
     del mv, outb
     del eng, out, w

@@ -536,3 +536,135 @@ def test_wide_stream_round_unmasks_clean():
     assert np.isfinite(out).all()
     assert np.abs(out).max() <= 1.0 + 1e-9
     assert np.abs(out).mean() > 1e-3
+
+
+# ------------------------------------------------ one value path, both widths
+
+
+def values_tensor(eng, ints):
+    """Python ints -> the engine's canonical value tensor ([n] or [2, n])."""
+    lo = np.array([v & (2**64 - 1) for v in ints], dtype=np.uint64)
+    if eng.wide:
+        lo = np.stack([lo, np.array([v >> 64 for v in ints], dtype=np.uint64)])
+    return torch.from_numpy(lo.view(np.int64)).to(eng.device)
+
+
+def values_ints(eng, t):
+    arr = t.cpu().numpy().view(np.uint64)
+    if eng.wide:
+        return [(int(h) << 64) + int(l) for l, h in zip(arr[0], arr[1])]
+    return [int(v) for v in arr]
+
+
+def random_values(order, n, seed):
+    import random
+
+    rng = random.Random(seed)
+    vals = [rng.randrange(order) for _ in range(n)]
+    vals[0], vals[-1] = 0, order - 1
+    return vals
+
+
+@pytest.mark.parametrize("cfg_args", [(1, 0, 0, 6), (0, 3, 0, 6)])
+def test_u64_planes_roundtrip(cfg_args):
+    """values_to_planes writes the host-computed 32-bit digits and ADDS (a
+    second call doubles them); planes_to_values returns 2v mod order. The
+    u64 mirror of test_gpu_wide_sharded.test_wide_recode_roundtrip."""
+    n = 1027
+    eng, c = make_engine(n, cfg_args)
+    assert not eng.wide
+    order = int(c.order)
+    vals = random_values(order, n, seed=21)
+    v = values_tensor(eng, vals)
+    digits = torch.tensor([[(x >> (32 * d)) & 0xFFFFFFFF for x in vals]
+                           for d in range(eng.n_digits)], dtype=torch.int64, device="cuda")
+
+    planes = torch.zeros(eng.n_digits, n, dtype=torch.int64, device="cuda")
+    eng.values_to_planes(v, planes)
+    assert torch.equal(planes, digits)
+    eng.values_to_planes(v, planes)
+    assert torch.equal(planes, 2 * digits)
+    back = torch.full_like(v, -1)
+    eng.planes_to_values(planes, back)
+    assert values_ints(eng, back) == [2 * x % order for x in vals]
+
+
+@pytest.mark.parametrize("cfg_args", [(1, 0, 0, 6), (1, 1, 0, 3)])
+def test_mod_add_values_on_shards(cfg_args):
+    """mod_add_values takes its length from the tensors: adding the two
+    column slices separately equals the full-length add and the exact sum."""
+    n, cut = 1027, 513
+    eng, c = make_engine(n, cfg_args)
+    order = int(c.order)
+    a_ints, b_ints = random_values(order, n, seed=31), random_values(order, n, seed=32)
+    b_ints[0] = order - 1  # (0 + order-1) and (order-1 + order-1) both occur
+    a, b = values_tensor(eng, a_ints), values_tensor(eng, b_ints)
+
+    full = a.clone()
+    eng.mod_add_values(full, b)
+    parts = a.clone()
+    for lo, hi in ((0, cut), (cut, n)):
+        if eng.wide:
+            eng.mod_add_values(parts[:, lo:hi], b[:, lo:hi])
+        else:
+            eng.mod_add_values(parts[lo:hi], b[lo:hi])
+    assert torch.equal(parts, full)
+    assert values_ints(eng, full) == [(x + y) % order for x, y in zip(a_ints, b_ints)]
+
+
+def raises_unchanged(call, out):
+    """call() raises ValueError and has not written to `out`."""
+    before = out.clone()
+    with pytest.raises(ValueError):
+        call()
+    assert torch.equal(out, before)
+
+
+@pytest.mark.parametrize("cfg_args", [(1, 0, 0, 6), (1, 1, 0, 3)])
+def test_value_and_plane_form_checks(cfg_args):
+    """Malformed value / plane tensors are rejected before any kernel runs."""
+    n = 130
+    eng, c = make_engine(n, cfg_args)
+    k = 2 if eng.wide else eng.n_digits
+
+    def i64(*shape):
+        return torch.full(shape, 7, dtype=torch.int64, device="cuda")
+
+    vals, out = eng.new_values(zero=True), eng.new_values().fill_(7)
+    planes = i64(k, n)
+    # a value tensor of the other width's rank
+    other = i64(n) if eng.wide else i64(2, n)
+    raises_unchanged(lambda: eng.planes_to_values(planes, other), other)
+    raises_unchanged(lambda: eng.values_to_planes(other, planes), planes)
+    raises_unchanged(lambda: eng.mod_add_values(out, other), out)
+    raises_unchanged(lambda: eng.mod_add_values(other, vals), other)
+    # values with stride(-1) != 1
+    wide_buf = eng.new_values(2 * n).fill_(7)
+    strided = wide_buf[..., ::2]
+    assert strided.shape == vals.shape and strided.stride(-1) == 2
+    raises_unchanged(lambda: eng.planes_to_values(planes, strided), wide_buf)
+    raises_unchanged(lambda: eng.values_to_planes(strided, planes), planes)
+    raises_unchanged(lambda: eng.mod_add_values(strided, vals), wide_buf)
+    raises_unchanged(lambda: eng.pack_wire(strided), wide_buf)
+    # non-contiguous planes
+    plane_buf = i64(k, 2 * n)
+    sliced = plane_buf[:, :n]
+    assert not sliced.is_contiguous()
+    raises_unchanged(lambda: eng.values_to_planes(vals, sliced), plane_buf)
+    raises_unchanged(lambda: eng.planes_to_values(sliced, out), out)
+    raises_unchanged(lambda: eng.unmask_planes(sliced, vals, 0, 1), plane_buf)
+    # planes whose n differs from the values'
+    longer = i64(k, n + 1)
+    raises_unchanged(lambda: eng.values_to_planes(vals, longer), longer)
+    raises_unchanged(lambda: eng.planes_to_values(longer, out), out)
+    raises_unchanged(lambda: eng.unmask_planes(longer, vals, 0, 1), longer)
+    if eng.wide:
+        return
+    # u64 orders: exactly n_digits planes of 32-bit digits
+    extra = i64(k + 1, n)
+    raises_unchanged(lambda: eng.values_to_planes(vals, extra), extra)
+    raises_unchanged(lambda: eng.planes_to_values(extra, out), out)
+    raises_unchanged(lambda: eng.unmask_planes(extra, vals, 0, 1), extra)
+    raises_unchanged(lambda: eng.values_to_planes(vals, planes, digit_bits=16), planes)
+    raises_unchanged(lambda: eng.planes_to_values(planes, out, digit_bits=16), out)
+    raises_unchanged(lambda: eng.unmask_planes(planes, vals, 0, 1, digit_bits=16), planes)

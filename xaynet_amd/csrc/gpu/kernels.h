@@ -2,8 +2,18 @@
 // hip_bindings.cpp. Both include this header, so a signature mismatch is a
 // compile error. All launches go to the null stream.
 //
+// One launcher per operation, for u64 and wide (u128) orders alike. An order
+// travels as (order_lo, order_hi) and is wide iff order_hi != 0 (order >=
+// 2^64); canonical values travel as (lo, hi) pointers to split u64 planes, hi
+// null for u64 orders. A launcher given the order picks its kernel by
+// order_hi, one without (pack, unpack, add_to_planes, K1 scatter) by the hi
+// pointer; the bindings reject calls in which the two disagree. This is the
+// only layer that chooses between the u64 and the u128 kernels.
+//
 // dtype arguments follow mask::DataType: 0=f32 1=f64 2=i32 3=i64 (integer
 // outputs truncate toward zero); anything else is hipErrorInvalidValue.
+// Digit planes are [n_planes][len]; u64 orders take 32-bit digits only, wide
+// orders digit_bits in 1..63.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -13,80 +23,60 @@
 extern "C" {
 
 // ---- K1: ChaCha20 mask expansion (candidates -> scan -> scatter) ----
-// u64 orders: each thread owns draws_per_thread = 16/words_per_draw attempts.
+// each thread owns attempts_per_thread = 16/words_per_draw attempts
 hipError_t xhip_k1_candidates(const uint32_t* key8_dev, uint64_t start_word,
                               uint64_t first_attempt, uint64_t n_attempts, int words_per_draw,
-                              int nbytes, uint64_t order, uint64_t* cand, uint32_t* wg_counts,
-                              int draws_per_thread, uint32_t* n_wgs_out);
-hipError_t xhip_k1_candidates_u128(const uint32_t* key8_dev, uint64_t start_word,
-                                   uint64_t first_attempt, uint64_t n_attempts,
-                                   int words_per_draw, int nbytes, uint64_t order_lo,
-                                   uint64_t order_hi, uint64_t* cand_lo, uint64_t* cand_hi,
-                                   uint32_t* wg_counts, int attempts_per_thread,
-                                   uint32_t* n_wgs_out);
+                              int nbytes, uint64_t order_lo, uint64_t order_hi,
+                              uint64_t* cand_lo, uint64_t* cand_hi, uint32_t* wg_counts,
+                              int attempts_per_thread, uint32_t* n_wgs_out);
 // blk_tmp must hold ceil(n/1024) u32
 hipError_t xhip_k1_scan_hier(uint32_t* wg_counts, uint32_t n, uint32_t* blk_tmp,
                              uint64_t* total_dev);
-hipError_t xhip_k1_scatter_compact(const uint64_t* cand, const uint32_t* wg_offsets,
-                                   const uint64_t* total_dev, uint32_t n_wgs, int dpt,
-                                   uint64_t out_base, uint64_t* out, uint64_t out_len);
-hipError_t xhip_k1_scatter_compact_u128(const uint64_t* cand_lo, const uint64_t* cand_hi,
-                                        const uint32_t* wg_offsets, const uint64_t* total_dev,
-                                        uint32_t n_wgs, int apt, uint64_t out_base,
-                                        uint64_t* out_lo, uint64_t* out_hi, uint64_t out_len);
+hipError_t xhip_k1_scatter_compact(const uint64_t* cand_lo, const uint64_t* cand_hi,
+                                   const uint32_t* wg_offsets, const uint64_t* total_dev,
+                                   uint32_t n_wgs, int apt, uint64_t out_base, uint64_t* out_lo,
+                                   uint64_t* out_hi, uint64_t out_len);
 
 // ---- K3: batched aggregation (ept <= 0 picks the per-bpn default) ----
 hipError_t xhip_k3_aggregate(uint64_t* acc, const uint8_t* updates, uint64_t stride,
                              uint32_t n_updates, uint64_t len, int bpn, int ept);
 
-// ---- K2/K4/K5/K6, u64 orders ----
-hipError_t xhip_k4_unmask(const uint64_t* acc, const uint64_t* mask, int dtype, void* out,
-                          uint64_t len, int n_digits, uint64_t order, uint64_t exp_shift,
-                          double n_add_shift, double scalar_sum);
+// ---- K2/K4: digit planes <-> canonical values, unmask ----
+hipError_t xhip_k4_unmask(const uint64_t* planes, const uint64_t* mask_lo,
+                          const uint64_t* mask_hi, int dtype, void* out, uint64_t len,
+                          int n_planes, int digit_bits, uint64_t order_lo, uint64_t order_hi,
+                          uint64_t exp_lo, uint64_t exp_hi, double n_add_shift,
+                          double scalar_sum);
+// u64 orders only: unmask (cross-rank sums of) canonical values
 hipError_t xhip_k4_unmask_values(const uint64_t* vals, const uint64_t* mask, int dtype,
                                  void* out, uint64_t len, uint64_t order, uint64_t exp_shift,
                                  double n_add_shift, double scalar_sum);
-hipError_t xhip_k2_canonicalize(const uint64_t* acc, uint64_t* out, uint64_t len, int n_digits,
-                                uint64_t order);
-hipError_t xhip_k2_mod_add_u64(uint64_t* a, const uint64_t* b, uint64_t len, uint64_t order);
-hipError_t xhip_k5_mask_pack(const uint64_t* mask, uint8_t* out, uint64_t len, int bpn,
-                             uint64_t order, uint64_t participant, double scalar,
-                             double add_shift, double exp_shift_d, uint64_t exp_shift);
-hipError_t xhip_k6_unpack_u64(const uint8_t* in, uint64_t* out, uint64_t len, int bpn);
-hipError_t xhip_k6_pack_u64(const uint64_t* in, uint8_t* out, uint64_t len, int bpn);
-hipError_t xhip_add_u64_to_planes(uint64_t* acc, const uint64_t* vals, uint64_t len,
-                                  int n_digits);
-
-// ---- K2/K4/K5/K6, u128 orders (split lo/hi u64 planes) ----
-hipError_t xhip_k2_canonicalize_u128(const uint64_t* acc, uint64_t* out_lo, uint64_t* out_hi,
-                                     uint64_t len, int n_digits, int digit_bits,
-                                     uint64_t order_lo, uint64_t order_hi);
-hipError_t xhip_add_u128_to_planes(uint64_t* planes, const uint64_t* lo, const uint64_t* hi,
-                                   uint64_t len, int k, int digit_bits);
-hipError_t xhip_k2_recode_planes_u128(const uint64_t* acc, uint64_t* out, uint64_t len,
-                                      int n_digits, uint64_t order_lo, uint64_t order_hi, int k,
-                                      int digit_bits);
-hipError_t xhip_k2_mod_add_u128(uint64_t* a_lo, uint64_t* a_hi, const uint64_t* b_lo,
-                                const uint64_t* b_hi, uint64_t len, uint64_t order_lo,
+hipError_t xhip_k2_canonicalize(const uint64_t* planes, uint64_t* out_lo, uint64_t* out_hi,
+                                uint64_t len, int n_planes, int digit_bits, uint64_t order_lo,
                                 uint64_t order_hi);
-hipError_t xhip_k6_unpack_u128(const uint8_t* in, uint64_t* out_lo, uint64_t* out_hi,
-                               uint64_t len, int bpn);
-hipError_t xhip_k6_pack_u128(const uint64_t* in_lo, const uint64_t* in_hi, uint8_t* out,
-                             uint64_t len, int bpn);
-hipError_t xhip_k4_unmask_u128(const uint64_t* acc, const uint64_t* mask_lo,
-                               const uint64_t* mask_hi, void* out, uint64_t len, int n_digits,
-                               int digit_bits, uint64_t order_lo, uint64_t order_hi,
-                               uint64_t exp_lo, uint64_t exp_hi, double n_add_shift,
-                               double scalar_sum, int dtype);
-hipError_t xhip_k5_mask_pack_u128(const uint64_t* mask_lo, const uint64_t* mask_hi, uint8_t* out,
-                                  uint64_t len, int bpn, uint64_t order_lo, uint64_t order_hi,
-                                  uint64_t participant, double scalar, double add_shift,
-                                  double exp_shift_d);
+hipError_t xhip_add_to_planes(uint64_t* planes, const uint64_t* lo, const uint64_t* hi,
+                              uint64_t len, int n_planes, int digit_bits);
+// wide orders only: 32-bit accumulator planes -> k compact planes
+hipError_t xhip_k2_recode_planes(const uint64_t* acc, uint64_t* out, uint64_t len, int n_digits,
+                                 uint64_t order_lo, uint64_t order_hi, int k, int digit_bits);
+hipError_t xhip_k2_mod_add(uint64_t* a_lo, uint64_t* a_hi, const uint64_t* b_lo,
+                           const uint64_t* b_hi, uint64_t len, uint64_t order_lo,
+                           uint64_t order_hi);
 
-// ---- K5w: mask real weights; wide = order > 2^64 ----
+// ---- K5: synthetic update rows, and masking of real weights ----
+hipError_t xhip_k5_mask_pack(const uint64_t* mask_lo, const uint64_t* mask_hi, uint8_t* out,
+                             uint64_t len, int bpn, uint64_t order_lo, uint64_t order_hi,
+                             uint64_t participant, double scalar, double add_shift,
+                             uint64_t exp_lo, uint64_t exp_hi);
 hipError_t xhip_k5_mask_weights(const void* w, int dtype, const uint64_t* mask_lo,
                                 const uint64_t* mask_hi, uint8_t* out, uint64_t len, int bpn,
                                 uint64_t order_lo, uint64_t order_hi, double scalar,
-                                double add_shift, uint64_t exp_lo, uint64_t exp_hi, int wide);
+                                double add_shift, uint64_t exp_lo, uint64_t exp_hi);
+
+// ---- K6: wire limbs <-> canonical values ----
+hipError_t xhip_k6_unpack(const uint8_t* in, uint64_t* out_lo, uint64_t* out_hi, uint64_t len,
+                          int bpn);
+hipError_t xhip_k6_pack(const uint64_t* in_lo, const uint64_t* in_hi, uint8_t* out, uint64_t len,
+                        int bpn);
 
 }  // extern "C"

@@ -1014,27 +1014,20 @@ static hipError_t dispatch_dtype(int dtype, F f) {
 
 hipError_t xhip_k1_candidates(const uint32_t* key8_dev, uint64_t start_word,
                               uint64_t first_attempt, uint64_t n_attempts, int words_per_draw,
-                              int nbytes, uint64_t order, uint64_t* cand, uint32_t* wg_counts,
-                              int draws_per_thread, uint32_t* n_wgs_out) {
-    uint32_t wgs = ceil_div_u32(n_attempts, uint64_t(K1_LDS_THREADS) * draws_per_thread);
-    *n_wgs_out = wgs;
-    hipLaunchKernelGGL(k1_candidates_lds, dim3(wgs), dim3(K1_LDS_THREADS), 0, 0, key8_dev,
-                       start_word, first_attempt, n_attempts, words_per_draw, nbytes, order,
-                       cand, wg_counts, draws_per_thread);
-    return hipGetLastError();
-}
-
-hipError_t xhip_k1_candidates_u128(const uint32_t* key8_dev, uint64_t start_word,
-                                   uint64_t first_attempt, uint64_t n_attempts,
-                                   int words_per_draw, int nbytes, uint64_t order_lo,
-                                   uint64_t order_hi, uint64_t* cand_lo, uint64_t* cand_hi,
-                                   uint32_t* wg_counts, int attempts_per_thread,
-                                   uint32_t* n_wgs_out) {
+                              int nbytes, uint64_t order_lo, uint64_t order_hi,
+                              uint64_t* cand_lo, uint64_t* cand_hi, uint32_t* wg_counts,
+                              int attempts_per_thread, uint32_t* n_wgs_out) {
     uint32_t wgs = ceil_div_u32(n_attempts, uint64_t(K1_LDS_THREADS) * attempts_per_thread);
     *n_wgs_out = wgs;
-    hipLaunchKernelGGL(k1_candidates_lds_u128, dim3(wgs), dim3(K1_LDS_THREADS), 0, 0, key8_dev,
-                       start_word, first_attempt, n_attempts, words_per_draw, nbytes, order_lo,
-                       order_hi, cand_lo, cand_hi, wg_counts, attempts_per_thread);
+    if (order_hi != 0)
+        hipLaunchKernelGGL(k1_candidates_lds_u128, dim3(wgs), dim3(K1_LDS_THREADS), 0, 0,
+                           key8_dev, start_word, first_attempt, n_attempts, words_per_draw,
+                           nbytes, order_lo, order_hi, cand_lo, cand_hi, wg_counts,
+                           attempts_per_thread);
+    else
+        hipLaunchKernelGGL(k1_candidates_lds, dim3(wgs), dim3(K1_LDS_THREADS), 0, 0, key8_dev,
+                           start_word, first_attempt, n_attempts, words_per_draw, nbytes,
+                           order_lo, cand_lo, wg_counts, attempts_per_thread);
     return hipGetLastError();
 }
 
@@ -1054,23 +1047,18 @@ hipError_t xhip_k1_scan_hier(uint32_t* wg_counts, uint32_t n, uint32_t* blk_tmp,
     return hipGetLastError();
 }
 
-hipError_t xhip_k1_scatter_compact(const uint64_t* cand, const uint32_t* wg_offsets,
-                                   const uint64_t* total_dev, uint32_t n_wgs, int dpt,
-                                   uint64_t out_base, uint64_t* out, uint64_t out_len) {
+hipError_t xhip_k1_scatter_compact(const uint64_t* cand_lo, const uint64_t* cand_hi,
+                                   const uint32_t* wg_offsets, const uint64_t* total_dev,
+                                   uint32_t n_wgs, int apt, uint64_t out_base, uint64_t* out_lo,
+                                   uint64_t* out_hi, uint64_t out_len) {
     if (n_wgs == 0) return hipSuccess;
-    hipLaunchKernelGGL(k1_scatter_compact, dim3(n_wgs), dim3(256), 0, 0, cand, wg_offsets,
-                       total_dev, n_wgs, 256 * dpt, out_base, out, out_len);
-    return hipGetLastError();
-}
-
-hipError_t xhip_k1_scatter_compact_u128(const uint64_t* cand_lo, const uint64_t* cand_hi,
-                                        const uint32_t* wg_offsets, const uint64_t* total_dev,
-                                        uint32_t n_wgs, int apt, uint64_t out_base,
-                                        uint64_t* out_lo, uint64_t* out_hi, uint64_t out_len) {
-    if (n_wgs == 0) return hipSuccess;
-    hipLaunchKernelGGL(k1_scatter_compact_u128, dim3(n_wgs), dim3(256), 0, 0, cand_lo, cand_hi,
-                       wg_offsets, total_dev, n_wgs, 256 * apt, out_base, out_lo, out_hi,
-                       out_len);
+    if (out_hi)
+        hipLaunchKernelGGL(k1_scatter_compact_u128, dim3(n_wgs), dim3(256), 0, 0, cand_lo,
+                           cand_hi, wg_offsets, total_dev, n_wgs, 256 * apt, out_base, out_lo,
+                           out_hi, out_len);
+    else
+        hipLaunchKernelGGL(k1_scatter_compact, dim3(n_wgs), dim3(256), 0, 0, cand_lo,
+                           wg_offsets, total_dev, n_wgs, 256 * apt, out_base, out_lo, out_len);
     return hipGetLastError();
 }
 
@@ -1157,16 +1145,38 @@ hipError_t xhip_k3_aggregate(uint64_t* acc, const uint8_t* updates, uint64_t str
     return hipGetLastError();
 }
 
-// ---- K2/K4/K5/K6, u64 orders ----
+// ---- K2/K4/K5/K6: the u64 or the u128 kernel, by the rule in kernels.h ----
 
-hipError_t xhip_k4_unmask(const uint64_t* acc, const uint64_t* mask, int dtype, void* out,
-                          uint64_t len, int n_digits, uint64_t order, uint64_t exp_shift,
-                          double n_add_shift, double scalar_sum) {
+// u64 kernels recombine 32-bit digits only. Wide kernels take any width in
+// 1..63: 32 (the accumulator layout) the compile-time variant, any other the
+// runtime-shift one.
+static bool bad_planes(bool wide, int n_planes, int digit_bits) {
+    if (n_planes < 1) return true;
+    return wide ? digit_bits < 1 || digit_bits > 63 : digit_bits != 32;
+}
+
+static double u128_to_double(uint64_t lo, uint64_t hi) {
+    return double(((unsigned __int128)hi << 64) | lo);  // one rounding
+}
+
+hipError_t xhip_k4_unmask(const uint64_t* planes, const uint64_t* mask_lo,
+                          const uint64_t* mask_hi, int dtype, void* out, uint64_t len,
+                          int n_planes, int digit_bits, uint64_t order_lo, uint64_t order_hi,
+                          uint64_t exp_lo, uint64_t exp_hi, double n_add_shift,
+                          double scalar_sum) {
+    const bool wide = order_hi != 0;
+    if (bad_planes(wide, n_planes, digit_bits) || (!wide && exp_hi)) return hipErrorInvalidValue;
     return dispatch_dtype(dtype, [&](auto t) {
         using OUT = typename decltype(t)::type;
-        return launch_1d(k4_unmask<OUT, decltype(t)::trunc>, len, acc, mask,
-                         static_cast<OUT*>(out), len, n_digits, order, exp_shift, n_add_shift,
-                         scalar_sum);
+        constexpr bool TRUNC = decltype(t)::trunc;
+        OUT* o = static_cast<OUT*>(out);
+        if (!wide)
+            return launch_1d(k4_unmask<OUT, TRUNC>, len, planes, mask_lo, o, len, n_planes,
+                             order_lo, exp_lo, n_add_shift, scalar_sum);
+        return launch_1d(digit_bits == 32 ? k4_unmask_u128<OUT, TRUNC, 32>
+                                          : k4_unmask_u128<OUT, TRUNC, 0>,
+                         len, planes, mask_lo, mask_hi, o, len, n_planes, digit_bits, order_lo,
+                         order_hi, exp_lo, exp_hi, n_add_shift, scalar_sum);
     });
 }
 
@@ -1181,112 +1191,72 @@ hipError_t xhip_k4_unmask_values(const uint64_t* vals, const uint64_t* mask, int
     });
 }
 
-hipError_t xhip_k2_canonicalize(const uint64_t* acc, uint64_t* out, uint64_t len, int n_digits,
-                                uint64_t order) {
-    return launch_1d(k2_canonicalize, len, acc, out, len, n_digits, order);
-}
-
-hipError_t xhip_k2_mod_add_u64(uint64_t* a, const uint64_t* b, uint64_t len, uint64_t order) {
-    return launch_1d(k2_mod_add_u64, len, a, b, len, order);
-}
-
-hipError_t xhip_k5_mask_pack(const uint64_t* mask, uint8_t* out, uint64_t len, int bpn,
-                             uint64_t order, uint64_t participant, double scalar,
-                             double add_shift, double exp_shift_d, uint64_t exp_shift) {
-    return launch_1d(k5_mask_pack, len, mask, out, len, bpn, order, participant, scalar,
-                     add_shift, exp_shift_d, exp_shift);
-}
-
-hipError_t xhip_k6_unpack_u64(const uint8_t* in, uint64_t* out, uint64_t len, int bpn) {
-    return launch_1d(k6_unpack_u64, len, in, out, len, bpn);
-}
-
-hipError_t xhip_k6_pack_u64(const uint64_t* in, uint8_t* out, uint64_t len, int bpn) {
-    return launch_1d(k6_pack_u64, len, in, out, len, bpn);
-}
-
-hipError_t xhip_add_u64_to_planes(uint64_t* acc, const uint64_t* vals, uint64_t len,
-                                  int n_digits) {
-    return launch_1d(k_add_u64_to_planes, len, acc, vals, len, n_digits);
-}
-
-// ---- K2/K4/K5/K6, u128 orders ----
-// digit_bits 32 (the accumulator layout) takes the compile-time variant; any
-// other width in 1..63 the runtime-shift one.
-
-hipError_t xhip_k2_canonicalize_u128(const uint64_t* acc, uint64_t* out_lo, uint64_t* out_hi,
-                                     uint64_t len, int n_digits, int digit_bits,
-                                     uint64_t order_lo, uint64_t order_hi) {
-    if (digit_bits < 1 || digit_bits > 63 || n_digits < 1) return hipErrorInvalidValue;
+hipError_t xhip_k2_canonicalize(const uint64_t* planes, uint64_t* out_lo, uint64_t* out_hi,
+                                uint64_t len, int n_planes, int digit_bits, uint64_t order_lo,
+                                uint64_t order_hi) {
+    const bool wide = order_hi != 0;
+    if (bad_planes(wide, n_planes, digit_bits)) return hipErrorInvalidValue;
+    if (!wide) return launch_1d(k2_canonicalize, len, planes, out_lo, len, n_planes, order_lo);
     return launch_1d(digit_bits == 32 ? k2_canonicalize_u128<32> : k2_canonicalize_u128<0>, len,
-                     acc, out_lo, out_hi, len, n_digits, digit_bits, order_lo, order_hi);
+                     planes, out_lo, out_hi, len, n_planes, digit_bits, order_lo, order_hi);
 }
 
-hipError_t xhip_add_u128_to_planes(uint64_t* planes, const uint64_t* lo, const uint64_t* hi,
-                                   uint64_t len, int k, int digit_bits) {
-    if (digit_bits < 1 || digit_bits > 63 || k < 1) return hipErrorInvalidValue;
-    return launch_1d(k_add_u128_to_planes, len, planes, lo, hi, len, k, digit_bits);
+hipError_t xhip_add_to_planes(uint64_t* planes, const uint64_t* lo, const uint64_t* hi,
+                              uint64_t len, int n_planes, int digit_bits) {
+    if (bad_planes(hi != nullptr, n_planes, digit_bits)) return hipErrorInvalidValue;
+    if (!hi) return launch_1d(k_add_u64_to_planes, len, planes, lo, len, n_planes);
+    return launch_1d(k_add_u128_to_planes, len, planes, lo, hi, len, n_planes, digit_bits);
 }
 
-hipError_t xhip_k2_recode_planes_u128(const uint64_t* acc, uint64_t* out, uint64_t len,
-                                      int n_digits, uint64_t order_lo, uint64_t order_hi, int k,
-                                      int digit_bits) {
-    if (digit_bits < 1 || digit_bits > 63 || k < 1 || n_digits < 1) return hipErrorInvalidValue;
+hipError_t xhip_k2_recode_planes(const uint64_t* acc, uint64_t* out, uint64_t len, int n_digits,
+                                 uint64_t order_lo, uint64_t order_hi, int k, int digit_bits) {
+    if (order_hi == 0 || bad_planes(true, k, digit_bits) || n_digits < 1)
+        return hipErrorInvalidValue;
     return launch_1d(k2_recode_planes_u128, len, acc, out, len, n_digits, order_lo, order_hi, k,
                      digit_bits);
 }
 
-hipError_t xhip_k2_mod_add_u128(uint64_t* a_lo, uint64_t* a_hi, const uint64_t* b_lo,
-                                const uint64_t* b_hi, uint64_t len, uint64_t order_lo,
-                                uint64_t order_hi) {
+hipError_t xhip_k2_mod_add(uint64_t* a_lo, uint64_t* a_hi, const uint64_t* b_lo,
+                           const uint64_t* b_hi, uint64_t len, uint64_t order_lo,
+                           uint64_t order_hi) {
+    if (order_hi == 0) return launch_1d(k2_mod_add_u64, len, a_lo, b_lo, len, order_lo);
     return launch_1d(k2_mod_add_u128, len, a_lo, a_hi, b_lo, b_hi, len, order_lo, order_hi);
 }
 
-hipError_t xhip_k6_unpack_u128(const uint8_t* in, uint64_t* out_lo, uint64_t* out_hi,
-                               uint64_t len, int bpn) {
-    return launch_1d(k6_unpack_u128, len, in, out_lo, out_hi, len, bpn);
+hipError_t xhip_k5_mask_pack(const uint64_t* mask_lo, const uint64_t* mask_hi, uint8_t* out,
+                             uint64_t len, int bpn, uint64_t order_lo, uint64_t order_hi,
+                             uint64_t participant, double scalar, double add_shift,
+                             uint64_t exp_lo, uint64_t exp_hi) {
+    const double exp_shift_d = u128_to_double(exp_lo, exp_hi);
+    if (order_hi != 0)
+        return launch_1d(k5_mask_pack_u128, len, mask_lo, mask_hi, out, len, bpn, order_lo,
+                         order_hi, participant, scalar, add_shift, exp_shift_d);
+    if (exp_hi) return hipErrorInvalidValue;
+    return launch_1d(k5_mask_pack, len, mask_lo, out, len, bpn, order_lo, participant, scalar,
+                     add_shift, exp_shift_d, exp_lo);
 }
-
-hipError_t xhip_k6_pack_u128(const uint64_t* in_lo, const uint64_t* in_hi, uint8_t* out,
-                             uint64_t len, int bpn) {
-    return launch_1d(k6_pack_u128, len, in_lo, in_hi, out, len, bpn);
-}
-
-hipError_t xhip_k4_unmask_u128(const uint64_t* acc, const uint64_t* mask_lo,
-                               const uint64_t* mask_hi, void* out, uint64_t len, int n_digits,
-                               int digit_bits, uint64_t order_lo, uint64_t order_hi,
-                               uint64_t exp_lo, uint64_t exp_hi, double n_add_shift,
-                               double scalar_sum, int dtype) {
-    if (digit_bits < 1 || digit_bits > 63 || n_digits < 1) return hipErrorInvalidValue;
-    return dispatch_dtype(dtype, [&](auto t) {
-        using OUT = typename decltype(t)::type;
-        constexpr bool TRUNC = decltype(t)::trunc;
-        return launch_1d(digit_bits == 32 ? k4_unmask_u128<OUT, TRUNC, 32>
-                                          : k4_unmask_u128<OUT, TRUNC, 0>,
-                         len, acc, mask_lo, mask_hi, static_cast<OUT*>(out), len, n_digits,
-                         digit_bits, order_lo, order_hi, exp_lo, exp_hi, n_add_shift,
-                         scalar_sum);
-    });
-}
-
-hipError_t xhip_k5_mask_pack_u128(const uint64_t* mask_lo, const uint64_t* mask_hi, uint8_t* out,
-                                  uint64_t len, int bpn, uint64_t order_lo, uint64_t order_hi,
-                                  uint64_t participant, double scalar, double add_shift,
-                                  double exp_shift_d) {
-    return launch_1d(k5_mask_pack_u128, len, mask_lo, mask_hi, out, len, bpn, order_lo, order_hi,
-                     participant, scalar, add_shift, exp_shift_d);
-}
-
-// ---- K5w ----
 
 hipError_t xhip_k5_mask_weights(const void* w, int dtype, const uint64_t* mask_lo,
                                 const uint64_t* mask_hi, uint8_t* out, uint64_t len, int bpn,
                                 uint64_t order_lo, uint64_t order_hi, double scalar,
-                                double add_shift, uint64_t exp_lo, uint64_t exp_hi, int wide) {
+                                double add_shift, uint64_t exp_lo, uint64_t exp_hi) {
     return dispatch_dtype(dtype, [&](auto t) {
         using T = typename decltype(t)::type;
-        return launch_1d(wide ? k5_mask_weights<T, true> : k5_mask_weights<T, false>, len,
-                         static_cast<const T*>(w), mask_lo, mask_hi, out, len, bpn, order_lo,
-                         order_hi, scalar, add_shift, exp_lo, exp_hi);
+        return launch_1d(order_hi != 0 ? k5_mask_weights<T, true> : k5_mask_weights<T, false>,
+                         len, static_cast<const T*>(w), mask_lo, mask_hi, out, len, bpn,
+                         order_lo, order_hi, scalar, add_shift, exp_lo, exp_hi);
     });
 }
+
+hipError_t xhip_k6_unpack(const uint8_t* in, uint64_t* out_lo, uint64_t* out_hi, uint64_t len,
+                          int bpn) {
+    if (!out_hi) return launch_1d(k6_unpack_u64, len, in, out_lo, len, bpn);
+    return launch_1d(k6_unpack_u128, len, in, out_lo, out_hi, len, bpn);
+}
+
+hipError_t xhip_k6_pack(const uint64_t* in_lo, const uint64_t* in_hi, uint8_t* out, uint64_t len,
+                        int bpn) {
+    if (!in_hi) return launch_1d(k6_pack_u64, len, in_lo, out, len, bpn);
+    return launch_1d(k6_pack_u128, len, in_lo, in_hi, out, len, bpn);
+}
+

@@ -35,7 +35,7 @@ class ParticipantAccel:
         # one accelerator may be shared by many participants (threads): the
         # engines + scratch are serialized under a lock
         self._mu = threading.Lock()
-        self._engines = {}  # (cfg8, length) -> (engine, total, scratch, cfgs)
+        self._engines = {}  # (cfg8, length) -> (engine, total, scratch)
 
     def _engine_for(self, cfg8, length: int):
         key = (tuple(cfg8), length)
@@ -46,13 +46,9 @@ class ParticipantAccel:
             from .engine import GpuMaskedAggregator
 
             mk = _core.mask
-            vect_cfg = mk.MaskConfig(*cfg8[:4])
-            unit_cfg = mk.MaskConfig(*cfg8[4:])
-            eng = GpuMaskedAggregator(vect_cfg, unit_cfg, length, device=self.device)
-            shape = (2, length) if eng.wide else (length,)
-            total = self.torch.zeros(*shape, dtype=self.torch.int64, device=eng.device)
-            scratch = self.torch.empty(*shape, dtype=self.torch.int64, device=eng.device)
-            ent = (eng, total, scratch, vect_cfg, unit_cfg)
+            eng = GpuMaskedAggregator(mk.MaskConfig(*cfg8[:4]), mk.MaskConfig(*cfg8[4:]), length,
+                                      device=self.device)
+            ent = (eng, eng.new_values(), eng.new_values())
             self._engines[key] = ent
         return ent
 
@@ -72,30 +68,9 @@ class ParticipantAccel:
     def aggregate_masks(self, seeds, length: int, cfg8):
         with self._mu:
             try:
-                eng, total, scratch, vect_cfg, unit_cfg = self._engine_for(cfg8, length)
-                total.zero_()
-                unit_order = int(unit_cfg.order)
-                unit_total = 0
-                for seed in seeds:
-                    eng.derive_mask_values(bytes(seed), out=scratch)
-                    eng.mod_add_values(total, scratch)
-                    unit_total = (unit_total + eng.unit_draw(bytes(seed))) % unit_order
-                limbs_dev = eng.pack_wire(total)
-                nlimb = length * eng.bpn
-                ubpn = unit_cfg.bytes_per_number
-                wire = bytearray(8 + nlimb + 4 + ubpn)
-                wire[0:4] = bytes(vect_cfg.to_bytes())
-                wire[4:8] = length.to_bytes(4, "big")
-                if getattr(eng, "_wire_pin", None) is None or eng._wire_pin.numel() < nlimb:
-                    eng._wire_pin = self.torch.empty(nlimb, dtype=self.torch.uint8,
-                                                     pin_memory=True)
-                pin = eng._wire_pin[:nlimb]
-                pin.copy_(limbs_dev)  # D2H at PCIe line rate (pinned)
-                np.frombuffer(wire, dtype=np.uint8, count=nlimb, offset=8)[:] = pin.numpy()
-                off = 8 + nlimb
-                wire[off : off + 4] = bytes(unit_cfg.to_bytes())
-                wire[off + 4 :] = unit_total.to_bytes(ubpn, "little")
-                return bytes(wire)
+                from .sum2 import aggregate_masks_on
+
+                return aggregate_masks_on(*self._engine_for(cfg8, length), seeds)
             except Exception:  # noqa: BLE001
                 LOG.exception("GPU sum2 hook failed; falling back to CPU")
                 return None

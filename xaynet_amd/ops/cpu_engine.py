@@ -24,46 +24,19 @@ import torch
 
 from xaynet_amd import _core
 
+from .base import MaskedAggregatorBase
+
 _U64 = np.uint64
 _M64 = (1 << 64) - 1
 
 
-class CpuPlaneAggregator:
+class CpuPlaneAggregator(MaskedAggregatorBase):
     """Digit-plane aggregation of wire-format masked updates on the CPU."""
 
-    _TORCH_DTYPES = {0: torch.float32, 1: torch.float64, 2: torch.int32, 3: torch.int64}
     _NP_DTYPES = {0: np.float32, 1: np.float64, 2: np.int32, 3: np.int64}
 
     def __init__(self, vect_cfg, unit_cfg, length: int, device: str = "cpu"):
-        if vect_cfg.bytes_per_number > 16:
-            raise ValueError("CpuPlaneAggregator covers group orders up to 2^128 "
-                             f"(got {vect_cfg.bytes_per_number} bytes/element)")
-        self.vect_cfg = vect_cfg
-        self.unit_cfg = unit_cfg
-        self.length = length
-        self.device = torch.device("cpu")
-        self.bpn = vect_cfg.bytes_per_number
-        self.wide = not vect_cfg.order_fits_u64
-        self.n_digits = (self.bpn + 3) // 4
-        self.order = vect_cfg.order
-        self.order_int = int(vect_cfg.order)
-        self.prng_nbytes = vect_cfg.prng_nbytes
-        self.acc = torch.zeros(self.n_digits, length, dtype=torch.int64)
-        self.nb_models = 0
-        self.unit_acc = 0
-
-    # ---------------- update staging ----------------
-
-    def row_stride(self) -> int:
-        raw = self.length * self.bpn + 16 * self.bpn
-        return (raw + 15) // 16 * 16
-
-    def alloc_update_pool(self, n: int) -> torch.Tensor:
-        return torch.empty(n, self.row_stride(), dtype=torch.uint8)
-
-    def upload_update(self, pool: torch.Tensor, row: int, wire_limbs: bytes):
-        t = torch.frombuffer(bytearray(wire_limbs), dtype=torch.uint8)
-        pool[row, : t.numel()].copy_(t)
+        super().__init__(vect_cfg, unit_cfg, length, "cpu")
 
     # ---------------- value tensors <-> python ints ----------------
 
@@ -132,10 +105,6 @@ class CpuPlaneAggregator:
         limbs = np.frombuffer(obj.vect_bytes, dtype=np.uint8).reshape(self.length, self.bpn)
         return self._ret(self._limbs_to_tensor(limbs), out)
 
-    def unit_draw(self, seed: bytes) -> int:
-        v, _ = _core.mask.unit_draw(seed, self.unit_cfg)
-        return int(v)
-
     # ---------------- aggregation ----------------
 
     def aggregate_pool(self, pool: torch.Tensor, n_updates: int, unit_sum: int = 0):
@@ -190,9 +159,6 @@ class CpuPlaneAggregator:
         s = av + bv  # safe: order < 2^63 on this path
         np.copyto(av, np.where(s >= order, s - order, s))
 
-    def add_values_to_planes(self, vals: torch.Tensor):
-        self.values_to_planes(vals, self.acc)
-
     def values_to_planes(self, vals: torch.Tensor, planes: torch.Tensor, digit_bits: int = 32):
         """Add canonical values into [k, n] planes of digit_bits-wide digits."""
         if self.wide:
@@ -217,24 +183,12 @@ class CpuPlaneAggregator:
         self._add_ints_to_planes(self._planes_to_ints(self.acc), out_planes, digit_bits)
         return out_planes
 
-    def _scalar_sum(self, mask_unit: int, nb: int) -> float:
-        from .engine import _cfg_scalars
-
-        info = _cfg_scalars(self.unit_cfg)
-        n1 = (self.unit_acc + int(self.unit_cfg.order) - mask_unit) % int(self.unit_cfg.order)
-        s = n1 / info["exp_shift"] - nb * info["add_shift"]
-        if s == 0:
-            raise ZeroDivisionError("scalar_sum is zero")
-        return s
-
-    def _finalize(self, masked: np.ndarray, mask: np.ndarray, nb: int, scalar_sum: float,
-                  dt: int) -> torch.Tensor:
-        """masked/mask: object-int arrays of canonical values."""
-        from .engine import _cfg_scalars
-
-        vinfo = _cfg_scalars(self.vect_cfg)
+    def _finalize(self, masked: np.ndarray, mask_values: torch.Tensor, mask_unit: int, nb: int,
+                  dtype: int | None) -> torch.Tensor:
+        """masked: object-int array of canonical values."""
+        scalar_sum, vinfo, dt = self._unmask_scalars(mask_unit, nb, dtype)
         order = self.order_int
-        t = (masked + order - mask) % order
+        t = (masked + order - self._ints(mask_values)) % order
         exp = vinfo["exp_shift_u64"]
         n_add = nb * vinfo["add_shift"]
         if self.wide:
@@ -253,29 +207,17 @@ class CpuPlaneAggregator:
     def unmask(self, mask_values: torch.Tensor, mask_unit: int,
                nb_models: int | None = None, dtype: int | None = None) -> torch.Tensor:
         nb = self.nb_models if nb_models is None else nb_models
-        dt = self.vect_cfg.dtype if dtype is None else dtype
-        masked = self._planes_to_ints(self.acc)
-        return self._finalize(masked, self._ints(mask_values), nb,
-                              self._scalar_sum(mask_unit, nb), dt)
+        return self._finalize(self._planes_to_ints(self.acc), mask_values, mask_unit, nb, dtype)
 
     def unmask_values(self, vals: torch.Tensor, mask_values: torch.Tensor, mask_unit: int,
                       nb_models: int, dtype: int | None = None) -> torch.Tensor:
         if self.wide:
             raise NotImplementedError("values unmask covers u64 orders")
-        dt = self.vect_cfg.dtype if dtype is None else dtype
         masked = vals.numpy().view(_U64).astype(object) % self.order_int
-        return self._finalize(masked, self._ints(mask_values), nb_models,
-                              self._scalar_sum(mask_unit, nb_models), dt)
+        return self._finalize(masked, mask_values, mask_unit, nb_models, dtype)
 
     def unmask_planes(self, planes: torch.Tensor, mask_values: torch.Tensor, mask_unit: int,
                       nb_models: int, dtype: int | None = None,
                       digit_bits: int = 32) -> torch.Tensor:
-        dt = self.vect_cfg.dtype if dtype is None else dtype
-        masked = self._planes_to_ints(planes, digit_bits)
-        return self._finalize(masked, self._ints(mask_values), nb_models,
-                              self._scalar_sum(mask_unit, nb_models), dt)
-
-    def reset(self):
-        self.acc.zero_()
-        self.nb_models = 0
-        self.unit_acc = 0
+        return self._finalize(self._planes_to_ints(planes, digit_bits), mask_values, mask_unit,
+                              nb_models, dtype)

@@ -13,11 +13,6 @@ Bmax orders beyond 2^128 stay on the CPU path.
 """
 from __future__ import annotations
 
-import numpy as np
-import torch
-
-from xaynet_amd import _core
-
 from .engine import GpuMaskedAggregator
 
 
@@ -26,30 +21,19 @@ def aggregate_masks(seeds, vect_cfg, unit_cfg, length: int, device: str = "cuda:
     aggregated MaskObject wire bytes (MaskVect || MaskUnit)."""
     if not seeds:
         raise ValueError("no seeds")
-    mk = _core.mask
     eng = GpuMaskedAggregator(vect_cfg, unit_cfg, length, device=device)
-    shape = (2, length) if eng.wide else (length,)
-    total = torch.zeros(*shape, dtype=torch.int64, device=eng.device)
-    scratch = torch.empty(*shape, dtype=torch.int64, device=eng.device)
-    unit_order = int(unit_cfg.order)
+    return aggregate_masks_on(eng, eng.new_values(), eng.new_values(), seeds)
+
+
+def aggregate_masks_on(eng, total, scratch, seeds) -> bytes:
+    """aggregate_masks on an existing engine and two of its `new_values()`
+    tensors (callers that serve many rounds keep all three)."""
+    total.zero_()
+    unit_order = int(eng.unit_cfg.order)
     unit_total = 0
     for seed in seeds:
+        seed = bytes(seed)
         eng.derive_mask_values(seed, out=scratch)
         eng.mod_add_values(total, scratch)
         unit_total = (unit_total + eng.unit_draw(seed)) % unit_order
-
-    limbs_dev = eng.pack_wire(total)
-    nlimb = length * eng.bpn
-    ubpn = unit_cfg.bytes_per_number
-    wire = bytearray(8 + nlimb + 4 + ubpn)
-    wire[0:4] = bytes(vect_cfg.to_bytes())
-    wire[4:8] = length.to_bytes(4, "big")
-    if getattr(eng, "_wire_pin", None) is None or eng._wire_pin.numel() < nlimb:
-        eng._wire_pin = torch.empty(nlimb, dtype=torch.uint8, pin_memory=True)
-    pin = eng._wire_pin[:nlimb]
-    pin.copy_(limbs_dev)  # D2H at PCIe line rate (pinned)
-    np.frombuffer(wire, dtype=np.uint8, count=nlimb, offset=8)[:] = pin.numpy()
-    off = 8 + nlimb
-    wire[off : off + 4] = bytes(unit_cfg.to_bytes())
-    wire[off + 4 :] = unit_total.to_bytes(ubpn, "little")
-    return bytes(wire)
+    return eng.wire_object(eng.pack_wire(total), unit_total)
