@@ -14,37 +14,64 @@
 
 namespace py = pybind11;
 
-// Orders and exp_shifts cross the Python boundary as decimal strings and the
-// launcher ABI as lo/hi halves.
-struct U128 {
-    uint64_t lo, hi;
+// Orders, exp_shifts and offsets cross the Python boundary as decimal strings
+// and the launcher ABI as five u64 limbs (xhip_limbs): values below 2^320.
+struct Limbs {
+    xhip_limbs v;
+    int n;  // limb count, ceil(bits / 64), at least 1
+
+    bool is_zero() const { return n == 1 && v.w[0] == 0; }
 };
 
-static U128 parse_u128(const std::string& dec) {
+static Limbs parse_limbs(const std::string& dec) {
     if (dec.empty()) throw std::runtime_error("bad decimal");
-    unsigned __int128 v = 0;
+    Limbs r{{{0, 0, 0, 0, 0}}, 1};
     for (char c : dec) {
         if (c < '0' || c > '9') throw std::runtime_error("bad decimal");
-        v = v * 10 + unsigned(c - '0');
+        uint64_t carry = unsigned(c - '0');
+        for (int j = 0; j < ML_MAX_LIMBS; ++j) {
+            unsigned __int128 t = (unsigned __int128)r.v.w[j] * 10 + carry;
+            r.v.w[j] = uint64_t(t);
+            carry = uint64_t(t >> 64);
+        }
+        if (carry) throw py::value_error("orders and shifts must be below 2^320");
     }
-    return {uint64_t(v), uint64_t(v >> 64)};
+    for (int j = 1; j < ML_MAX_LIMBS; ++j)
+        if (r.v.w[j]) r.n = j + 1;
+    return r;
+}
+
+// an optional constant: the empty string is 0
+static Limbs parse_optional(const std::string& dec) {
+    if (dec.empty()) return Limbs{{{0, 0, 0, 0, 0}}, 1};
+    return parse_limbs(dec);
 }
 
 // The one width rule: an order is wide iff it is >= 2^64, and canonical
 // values are a (lo, hi) pointer pair whose hi is null exactly for u64 orders.
-// Checked before any HIP call; the launchers rely on it.
-static U128 parse_order(const std::string& dec, uintptr_t hi_ptr) {
-    U128 o = parse_u128(dec);
-    if ((hi_ptr != 0) != (o.hi != 0))
-        throw py::value_error(o.hi ? "order >= 2^64 takes split lo/hi values (hi pointer is null)"
+// For wide orders lo and hi are limb rows 0 and 1, and row j of the order's
+// ceil(bits/64) rows lives at lo + j*(hi - lo). Checked before any HIP call;
+// the launchers rely on it.
+static Limbs parse_order(const std::string& dec, uintptr_t hi_ptr) {
+    Limbs o = parse_limbs(dec);
+    const bool wide = o.n > 1;
+    if ((hi_ptr != 0) != wide)
+        throw py::value_error(wide ? "order >= 2^64 takes split lo/hi values (hi pointer is null)"
                                    : "order < 2^64 takes plain u64 values (hi pointer is set)");
     return o;
 }
 
 // u64-order digit planes are 32 bits wide (the u64 kernels know no other).
-static void check_digit_bits(const U128& order, int digit_bits) {
-    if (order.hi == 0 && digit_bits != 32)
+static void check_digit_bits(const Limbs& order, int digit_bits) {
+    if (order.n == 1 && digit_bits != 32)
         throw py::value_error("u64-order digit planes are 32 bits wide");
+}
+
+// a constant as a long double (x86: 64-bit mantissa)
+static long double limbs_to_ld(const Limbs& a) {
+    long double r = 0;
+    for (int j = a.n - 1; j >= 0; --j) r = r * 18446744073709551616.0L + (long double)a.v.w[j];
+    return r;
 }
 
 static uint64_t* u64p(uintptr_t p) { return reinterpret_cast<uint64_t*>(p); }
@@ -109,15 +136,20 @@ class MaskExpander {
     uint64_t expand(const std::string& seed, uintptr_t out_lo_ptr, uintptr_t out_hi_ptr,
                     uint64_t len, const std::string& order_dec, int prng_nbytes,
                     uint64_t start_word) {
-        const U128 order = parse_order(order_dec, out_hi_ptr);
-        const bool wide = order.hi != 0;
+        const Limbs order = parse_order(order_dec, out_hi_ptr);
+        const int L = order.n;
         if (seed.size() != 32) throw py::value_error("seed must be 32 bytes");
-        if (prng_nbytes < (wide ? 9 : 1) || prng_nbytes > (wide ? 16 : 8))
-            throw py::value_error("prng_nbytes must be 1..8 for u64 orders, 9..16 for wide");
-        const int wpd = (prng_nbytes + 3) / 4;  // keystream words per attempt: 1..4
+        const int lo_bytes = L == 1 ? 1 : L == 2 ? 9 : 17, hi_bytes = L <= 2 ? 8 * L : 40;
+        if (prng_nbytes < lo_bytes || prng_nbytes > hi_bytes || prng_nbytes > 8 * L)
+            throw py::value_error(
+                "prng_nbytes must be 1..8 for u64 orders, 9..16 for u128, 17..40 beyond");
+        if (len == 0) return 0;
+        const int wpd = (prng_nbytes + 3) / 4;  // keystream words per attempt: 1..10
         const int apt = 16 / wpd;  // attempts per candidates thread (workgroups cover 256 * apt)
-        const double p = (double(order.hi) * 18446744073709551616.0 + double(order.lo)) *
-                         std::pow(2.0, -8.0 * prng_nbytes);  // acceptance
+        const double order_d =
+            L <= 2 ? double(order.v.w[1]) * 18446744073709551616.0 + double(order.v.w[0])
+                   : double(limbs_to_ld(order));
+        const double p = order_d * std::pow(2.0, -8.0 * prng_nbytes);  // acceptance
         uint64_t* out_lo = u64p(out_lo_ptr);
         uint64_t* out_hi = u64p(out_hi_ptr);
 
@@ -130,23 +162,30 @@ class MaskExpander {
             uint64_t remaining = len - filled;
             double exp_att = double(remaining) / p;
             uint64_t n_att = uint64_t(exp_att + 6.0 * std::sqrt(exp_att / p) + 1024.0);
+            // multi-limb orders accept as few as 1 draw in 200: cap the launch
+            // so the workspace does not grow with 1/p, and loop
+            if (L > 2 && n_att > kMaxAttemptsPerLaunch) n_att = kMaxAttemptsPerLaunch;
             // accepted draws compact into per-workgroup segments of `cand`,
             // the last one cut at n_att; counts: one per workgroup
             uint64_t max_wgs = (n_att + 256 * apt - 1) / (256 * apt) + 2;
-            cand_lo_.reserve(n_att, "alloc cand");
-            if (wide) cand_hi_.reserve(n_att, "alloc cand_hi");
+            // candidate limb planes: one buffer each for lo and hi, or for
+            // multi-limb orders L planes of n_att in the first
+            cand_lo_.reserve(L > 2 ? L * n_att : n_att, "alloc cand");
+            if (L == 2) cand_hi_.reserve(n_att, "alloc cand_hi");
+            uint64_t* cand_hi = L > 2 ? cand_lo_.get() + n_att : cand_hi_.get();
             counts_.reserve(max_wgs, "alloc counts");
             scan_tmp_.reserve(max_wgs / 1024 + 2, "alloc scan tmp");
 
             uint32_t n_wgs = 0;
-            check(xhip_k1_candidates(key_.get(), start_word, attempt, n_att, wpd, prng_nbytes,
-                                     order.lo, order.hi, cand_lo_.get(), cand_hi_.get(),
-                                     counts_.get(), apt, &n_wgs),
+            check(xhip_k1_candidates_limbs(key_.get(), start_word, attempt, n_att, wpd,
+                                           prng_nbytes, order.v, cand_lo_.get(), cand_hi,
+                                           counts_.get(), apt, &n_wgs),
                   "k1_candidates");
             check(xhip_k1_scan_hier(counts_.get(), n_wgs, scan_tmp_.get(), total_.get()),
                   "k1_scan");
-            check(xhip_k1_scatter_compact(cand_lo_.get(), cand_hi_.get(), counts_.get(),
-                                          total_.get(), n_wgs, apt, filled, out_lo, out_hi, len),
+            check(xhip_k1_scatter_compact_limbs(cand_lo_.get(), cand_hi, counts_.get(),
+                                                total_.get(), n_wgs, apt, filled, out_lo, out_hi,
+                                                len, order.v),
                   "k1_scatter_compact");
             uint64_t round_accepted = 0;
             check(hipMemcpy(&round_accepted, total_.get(), 8, hipMemcpyDeviceToHost),
@@ -161,8 +200,11 @@ class MaskExpander {
     }
 
   private:
-    DeviceBuffer<uint64_t> cand_lo_;  // the only candidate plane of u64 orders
-    DeviceBuffer<uint64_t> cand_hi_;  // wide orders only
+    // 2^22 attempts: 160 MiB of candidate planes at five limbs
+    static constexpr uint64_t kMaxAttemptsPerLaunch = uint64_t(1) << 22;
+
+    DeviceBuffer<uint64_t> cand_lo_;  // u64 orders' only plane; every plane of multi-limb ones
+    DeviceBuffer<uint64_t> cand_hi_;  // u128 orders only
     DeviceBuffer<uint32_t> counts_;   // accepted per candidates workgroup
     DeviceBuffer<uint32_t> scan_tmp_;
     DeviceBuffer<uint64_t> total_;
@@ -193,7 +235,8 @@ PYBIND11_MODULE(_hip, m) {
 
     // Every function below that takes canonical values takes them as
     // (lo, hi) device pointers plus the order as a decimal string; see
-    // parse_order. exp_shift is a decimal string too (10^20 for f64 configs).
+    // parse_order. exp_shift is a decimal string too (10^20 for f64 configs,
+    // 10^45 for f32 Bmax).
     py::class_<MaskExpander>(m, "MaskExpander")
         .def(py::init<>())
         .def("expand", &MaskExpander::expand, py::arg("seed"), py::arg("out_lo"),
@@ -212,22 +255,41 @@ PYBIND11_MODULE(_hip, m) {
 
     // [n_planes][len] digit planes minus the mask -> model weights.
     // dtype follows mask::DataType: 0=F32 1=F64 2=I32 3=I64
+    // Bmax configs pass `offset` = nb * add_shift * exp_shift as a decimal
+    // string: the shift is then subtracted in integers (n_add_shift is unused),
+    // and `divisor`, where exp_shift * scalar_sum is an exact integer below
+    // 2^64, makes integer outputs the exact truncated quotient.
     m.def(
         "unmask",
         [](uintptr_t planes, uintptr_t mask_lo, uintptr_t mask_hi, uintptr_t out, uint64_t len,
            int n_planes, const std::string& order, const std::string& exp_shift,
-           double n_add_shift, double scalar_sum, int dtype, int digit_bits) {
-            U128 o = parse_order(order, mask_hi), e = parse_u128(exp_shift);
+           double n_add_shift, double scalar_sum, int dtype, int digit_bits,
+           const std::string& offset, const std::string& divisor) {
+            Limbs o = parse_order(order, mask_hi), e = parse_limbs(exp_shift);
+            Limbs off = parse_optional(offset), div = parse_optional(divisor);
             check_digit_bits(o, digit_bits);
-            check(xhip_k4_unmask(u64p(planes), u64p(mask_lo), u64p(mask_hi), dtype,
-                                 reinterpret_cast<void*>(out), len, n_planes, digit_bits, o.lo,
-                                 o.hi, e.lo, e.hi, n_add_shift, scalar_sum),
+            if (off.is_zero()) {
+                if (o.n > 2)
+                    throw py::value_error("orders >= 2^128 are Bmax configs: unmask needs "
+                                          "their exact offset");
+                if (e.n > 2) throw py::value_error("exp_shift >= 2^128 needs the exact offset");
+                if (!div.is_zero()) throw py::value_error("divisor goes with an offset");
+            } else if (o.n < 2 || off.n > o.n) {
+                throw py::value_error("the exact offset must be below the (wide) order");
+            }
+            if (div.n > 1) throw py::value_error("divisor must be below 2^64");
+            // 1 / (exp_shift * scalar_sum), rounded to a double once
+            const double scale = double(1.0L / (limbs_to_ld(e) * (long double)scalar_sum));
+            check(xhip_k4_unmask_limbs(u64p(planes), u64p(mask_lo), u64p(mask_hi), dtype,
+                                       reinterpret_cast<void*>(out), len, n_planes, digit_bits,
+                                       o.v, e.v, n_add_shift, scalar_sum, off.v, div.v.w[0],
+                                       scale),
                   "k4_unmask");
         },
         py::arg("planes"), py::arg("mask_lo"), py::arg("mask_hi"), py::arg("out"),
         py::arg("len"), py::arg("n_planes"), py::arg("order"), py::arg("exp_shift"),
         py::arg("n_add_shift"), py::arg("scalar_sum"), py::arg("dtype") = 0,
-        py::arg("digit_bits") = 32, nogil);
+        py::arg("digit_bits") = 32, py::arg("offset") = "", py::arg("divisor") = "", nogil);
 
     // u64 orders only: `vals` are plain u64 (cross-rank sums of) canonical values
     m.def(
@@ -235,10 +297,10 @@ PYBIND11_MODULE(_hip, m) {
         [](uintptr_t vals, uintptr_t mask_lo, uintptr_t mask_hi, uintptr_t out, uint64_t len,
            const std::string& order, const std::string& exp_shift, double n_add_shift,
            double scalar_sum, int dtype) {
-            U128 o = parse_order(order, mask_hi), e = parse_u128(exp_shift);
-            if (o.hi || e.hi) throw py::value_error("unmask_values covers u64 orders");
+            Limbs o = parse_order(order, mask_hi), e = parse_limbs(exp_shift);
+            if (o.n > 1 || e.n > 1) throw py::value_error("unmask_values covers u64 orders");
             check(xhip_k4_unmask_values(u64p(vals), u64p(mask_lo), dtype,
-                                        reinterpret_cast<void*>(out), len, o.lo, e.lo,
+                                        reinterpret_cast<void*>(out), len, o.v.w[0], e.v.w[0],
                                         n_add_shift, scalar_sum),
                   "k4_unmask_values");
         },
@@ -251,10 +313,10 @@ PYBIND11_MODULE(_hip, m) {
         "canonicalize",
         [](uintptr_t planes, uintptr_t out_lo, uintptr_t out_hi, uint64_t len, int n_planes,
            const std::string& order, int digit_bits) {
-            U128 o = parse_order(order, out_hi);
+            Limbs o = parse_order(order, out_hi);
             check_digit_bits(o, digit_bits);
-            check(xhip_k2_canonicalize(u64p(planes), u64p(out_lo), u64p(out_hi), len, n_planes,
-                                       digit_bits, o.lo, o.hi),
+            check(xhip_k2_canonicalize_limbs(u64p(planes), u64p(out_lo), u64p(out_hi), len,
+                                             n_planes, digit_bits, o.v),
                   "k2_canonicalize");
         },
         py::arg("planes"), py::arg("out_lo"), py::arg("out_hi"), py::arg("len"),
@@ -265,9 +327,10 @@ PYBIND11_MODULE(_hip, m) {
         "add_to_planes",
         [](uintptr_t planes, uintptr_t lo, uintptr_t hi, uint64_t len, int n_planes,
            const std::string& order, int digit_bits) {
-            check_digit_bits(parse_order(order, hi), digit_bits);
-            check(xhip_add_to_planes(u64p(planes), u64p(lo), u64p(hi), len, n_planes,
-                                     digit_bits),
+            Limbs o = parse_order(order, hi);
+            check_digit_bits(o, digit_bits);
+            check(xhip_add_to_planes_limbs(u64p(planes), u64p(lo), u64p(hi), len, n_planes,
+                                           digit_bits, o.v),
                   "add_to_planes");
         },
         py::arg("planes"), py::arg("lo"), py::arg("hi"), py::arg("len"), py::arg("n_planes"),
@@ -279,10 +342,10 @@ PYBIND11_MODULE(_hip, m) {
         "recode_planes",
         [](uintptr_t acc, uintptr_t out, uint64_t len, int n_digits, const std::string& order,
            int k, int digit_bits) {
-            U128 o = parse_u128(order);
-            if (!o.hi) throw py::value_error("recode_planes covers wide (u128) orders");
-            check(xhip_k2_recode_planes(u64p(acc), u64p(out), len, n_digits, o.lo, o.hi, k,
-                                        digit_bits),
+            Limbs o = parse_limbs(order);
+            if (o.n == 1) throw py::value_error("recode_planes covers wide (>= 2^64) orders");
+            check(xhip_k2_recode_planes_limbs(u64p(acc), u64p(out), len, n_digits, o.v, k,
+                                              digit_bits),
                   "k2_recode_planes");
         },
         py::arg("acc"), py::arg("out"), py::arg("len"), py::arg("n_digits"), py::arg("order"),
@@ -293,10 +356,10 @@ PYBIND11_MODULE(_hip, m) {
         "mod_add",
         [](uintptr_t a_lo, uintptr_t a_hi, uintptr_t b_lo, uintptr_t b_hi, uint64_t len,
            const std::string& order) {
-            U128 o = parse_order(order, a_hi);
+            Limbs o = parse_order(order, a_hi);
             parse_order(order, b_hi);
-            check(xhip_k2_mod_add(u64p(a_lo), u64p(a_hi), u64p(b_lo), u64p(b_hi), len, o.lo,
-                                  o.hi),
+            check(xhip_k2_mod_add_limbs(u64p(a_lo), u64p(a_hi), u64p(b_lo), u64p(b_hi), len,
+                                        o.v),
                   "k2_mod_add");
         },
         py::arg("a_lo"), py::arg("a_hi"), py::arg("b_lo"), py::arg("b_hi"), py::arg("len"),
@@ -308,38 +371,49 @@ PYBIND11_MODULE(_hip, m) {
         [](uintptr_t mask_lo, uintptr_t mask_hi, uintptr_t out, uint64_t len, int bpn,
            const std::string& order, uint64_t participant, double scalar, double add_shift,
            const std::string& exp_shift) {
-            U128 o = parse_order(order, mask_hi), e = parse_u128(exp_shift);
-            check(xhip_k5_mask_pack(u64p(mask_lo), u64p(mask_hi), u8p(out), len, bpn, o.lo, o.hi,
-                                    participant, scalar, add_shift, e.lo, e.hi),
+            Limbs o = parse_order(order, mask_hi), e = parse_limbs(exp_shift);
+            if (o.n > 2 || e.n > 2)
+                throw py::value_error("synthetic update rows cover orders up to 2^128");
+            check(xhip_k5_mask_pack(u64p(mask_lo), u64p(mask_hi), u8p(out), len, bpn, o.v.w[0],
+                                    o.v.w[1], participant, scalar, add_shift, e.v.w[0],
+                                    e.v.w[1]),
                   "k5_mask_pack");
         },
         py::arg("mask_lo"), py::arg("mask_hi"), py::arg("out"), py::arg("len"), py::arg("bpn"),
         py::arg("order"), py::arg("participant"), py::arg("scalar"), py::arg("add_shift"),
         py::arg("exp_shift"), nogil);
 
-    // real weights (dtype as for unmask): quantize, add the mask, pack
+    // real weights (dtype as for unmask): quantize, add the mask, pack. Bmax
+    // configs pass `offset` = add_shift * exp_shift as a decimal string, which
+    // is then added in integers.
     m.def(
         "mask_weights",
         [](uintptr_t w, int dtype, uintptr_t mask_lo, uintptr_t mask_hi, uintptr_t out,
            uint64_t len, int bpn, const std::string& order, double scalar, double add_shift,
-           const std::string& exp_shift) {
-            U128 o = parse_order(order, mask_hi), e = parse_u128(exp_shift);
-            check(xhip_k5_mask_weights(reinterpret_cast<const void*>(w), dtype, u64p(mask_lo),
-                                       u64p(mask_hi), u8p(out), len, bpn, o.lo, o.hi, scalar,
-                                       add_shift, e.lo, e.hi),
+           const std::string& exp_shift, const std::string& offset) {
+            Limbs o = parse_order(order, mask_hi), e = parse_limbs(exp_shift);
+            Limbs off = parse_optional(offset);
+            if (off.is_zero() ? (o.n > 2 || e.n > 2) : (o.n < 2 || off.n > o.n || e.n > o.n))
+                throw py::value_error(
+                    "mask_weights: orders >= 2^128 (Bmax) need offset = add_shift * exp_shift, "
+                    "below the order");
+            check(xhip_k5_mask_weights_limbs(reinterpret_cast<const void*>(w), dtype,
+                                             u64p(mask_lo), u64p(mask_hi), u8p(out), len, bpn,
+                                             o.v, scalar, add_shift, e.v, off.v),
                   "k5_mask_weights");
         },
         py::arg("w"), py::arg("dtype"), py::arg("mask_lo"), py::arg("mask_hi"), py::arg("out"),
         py::arg("len"), py::arg("bpn"), py::arg("order"), py::arg("scalar"),
-        py::arg("add_shift"), py::arg("exp_shift"), nogil);
+        py::arg("add_shift"), py::arg("exp_shift"), py::arg("offset") = "", nogil);
 
     // canonical values <-> packed wire limbs of bpn bytes
     m.def(
         "pack",
         [](uintptr_t in_lo, uintptr_t in_hi, uintptr_t out, uint64_t len, int bpn,
            const std::string& order) {
-            parse_order(order, in_hi);
-            check(xhip_k6_pack(u64p(in_lo), u64p(in_hi), u8p(out), len, bpn), "k6_pack");
+            Limbs o = parse_order(order, in_hi);
+            check(xhip_k6_pack_limbs(u64p(in_lo), u64p(in_hi), u8p(out), len, bpn, o.v),
+                  "k6_pack");
         },
         py::arg("in_lo"), py::arg("in_hi"), py::arg("out"), py::arg("len"), py::arg("bpn"),
         py::arg("order"), nogil);
@@ -347,8 +421,9 @@ PYBIND11_MODULE(_hip, m) {
         "unpack",
         [](uintptr_t in, uintptr_t out_lo, uintptr_t out_hi, uint64_t len, int bpn,
            const std::string& order) {
-            parse_order(order, out_hi);
-            check(xhip_k6_unpack(u8p(in), u64p(out_lo), u64p(out_hi), len, bpn), "k6_unpack");
+            Limbs o = parse_order(order, out_hi);
+            check(xhip_k6_unpack_limbs(u8p(in), u64p(out_lo), u64p(out_hi), len, bpn, o.v),
+                  "k6_unpack");
         },
         py::arg("packed"), py::arg("out_lo"), py::arg("out_hi"), py::arg("len"), py::arg("bpn"),
         py::arg("order"), nogil);

@@ -7,8 +7,11 @@
 // 2^64); canonical values travel as (lo, hi) pointers to split u64 planes, hi
 // null for u64 orders. A launcher given the order picks its kernel by
 // order_hi, one without (pack, unpack, add_to_planes, K1 scatter) by the hi
-// pointer; the bindings reject calls in which the two disagree. This is the
-// only layer that chooses between the u64 and the u128 kernels.
+// pointer; the bindings reject calls in which the two disagree. A third width
+// class, multi-limb orders in [2^128, 2^320), enters through the *_limbs
+// launchers at the end, which the bindings call for every width. This is the
+// only layer that chooses between the u64, the u128 and the multi-limb
+// kernels.
 //
 // dtype arguments follow mask::DataType: 0=f32 1=f64 2=i32 3=i64 (integer
 // outputs truncate toward zero); anything else is hipErrorInvalidValue.
@@ -19,6 +22,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+
+#include "limbs.h"
 
 extern "C" {
 
@@ -78,5 +83,55 @@ hipError_t xhip_k6_unpack(const uint8_t* in, uint64_t* out_lo, uint64_t* out_hi,
                           int bpn);
 hipError_t xhip_k6_pack(const uint64_t* in_lo, const uint64_t* in_hi, uint8_t* out, uint64_t len,
                         int bpn);
+
+// ---- every width: u64, u128 and multi-limb orders below 2^320 ----
+//
+// The launchers the bindings call. The order travels by value as five u64
+// limbs (xhip_limbs, limbs.h) and its limb count L = ceil(bits/64) is the
+// width: L <= 2 forwards to the launcher above, L = 3..5 runs the multi-limb
+// kernels. Canonical values stay a (lo, hi) pointer pair: for L >= 2 lo is
+// limb row 0, hi row 1, and row j lives at lo + j*(hi - lo), so a column
+// slice of an [L, n] tensor works as it does for [2, n].
+hipError_t xhip_k1_candidates_limbs(const uint32_t* key8_dev, uint64_t start_word,
+                                    uint64_t first_attempt, uint64_t n_attempts,
+                                    int words_per_draw, int nbytes, xhip_limbs order,
+                                    uint64_t* cand_lo, uint64_t* cand_hi, uint32_t* wg_counts,
+                                    int attempts_per_thread, uint32_t* n_wgs_out);
+hipError_t xhip_k1_scatter_compact_limbs(const uint64_t* cand_lo, const uint64_t* cand_hi,
+                                         const uint32_t* wg_offsets, const uint64_t* total_dev,
+                                         uint32_t n_wgs, int apt, uint64_t out_base,
+                                         uint64_t* out_lo, uint64_t* out_hi, uint64_t out_len,
+                                         xhip_limbs order);
+// offset == 0: the shift-in-doubles unmask of the B0..B6 bounds (L <= 2,
+// exp_shift below 2^128). offset != 0 (Bmax, L = 2..5): the exact-offset
+// unmask, weight = (t - offset) / (exp_shift * scalar_sum); n_add_shift is
+// unused, `divisor` is exp_shift * scalar_sum where that is an exact integer
+// below 2^64 (else 0) and `scale` the double nearest 1/(exp_shift *
+// scalar_sum). Integer dtypes need a one-word exp_shift.
+hipError_t xhip_k4_unmask_limbs(const uint64_t* planes, const uint64_t* mask_lo,
+                                const uint64_t* mask_hi, int dtype, void* out, uint64_t len,
+                                int n_planes, int digit_bits, xhip_limbs order,
+                                xhip_limbs exp_shift, double n_add_shift, double scalar_sum,
+                                xhip_limbs offset, uint64_t divisor, double scale);
+hipError_t xhip_k2_canonicalize_limbs(const uint64_t* planes, uint64_t* out_lo,
+                                      uint64_t* out_hi, uint64_t len, int n_planes,
+                                      int digit_bits, xhip_limbs order);
+hipError_t xhip_add_to_planes_limbs(uint64_t* planes, const uint64_t* lo, const uint64_t* hi,
+                                    uint64_t len, int n_planes, int digit_bits,
+                                    xhip_limbs order);
+hipError_t xhip_k2_recode_planes_limbs(const uint64_t* acc, uint64_t* out, uint64_t len,
+                                       int n_digits, xhip_limbs order, int k, int digit_bits);
+hipError_t xhip_k2_mod_add_limbs(uint64_t* a_lo, uint64_t* a_hi, const uint64_t* b_lo,
+                                 const uint64_t* b_hi, uint64_t len, xhip_limbs order);
+// offset == 0: the B0..B6 kernel (L <= 2). offset = add_shift * exp_shift
+// (Bmax, L = 2..5): quantise and add the shift in integers.
+hipError_t xhip_k5_mask_weights_limbs(const void* w, int dtype, const uint64_t* mask_lo,
+                                      const uint64_t* mask_hi, uint8_t* out, uint64_t len,
+                                      int bpn, xhip_limbs order, double scalar, double add_shift,
+                                      xhip_limbs exp_shift, xhip_limbs offset);
+hipError_t xhip_k6_unpack_limbs(const uint8_t* in, uint64_t* out_lo, uint64_t* out_hi,
+                                uint64_t len, int bpn, xhip_limbs order);
+hipError_t xhip_k6_pack_limbs(const uint64_t* in_lo, const uint64_t* in_hi, uint8_t* out,
+                              uint64_t len, int bpn, xhip_limbs order);
 
 }  // extern "C"

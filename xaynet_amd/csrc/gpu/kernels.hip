@@ -26,9 +26,11 @@
 //    prefix-scan compaction assigns the j-th ACCEPTED attempt to element j —
 //    bit-identical to the reference's sequential walk.
 //
-// This file covers group orders up to 2^128 (bpn <= 16): orders < 2^64 keep
-// canonical values in one u64, wider ones in split lo/hi u64 planes (the
-// *_u128 kernels). Only Bmax orders beyond 2^128 take the CPU oracle.
+// This file covers group orders below 2^320 (bpn <= 40): orders < 2^64 keep
+// canonical values in one u64, orders up to 2^128 in split lo/hi u64 planes
+// (the *_u128 kernels), wider ones in 3..5 rows of u64 limbs (the *_ml
+// kernels; the f32 and i64 Bmax configs). Only f64 Bmax orders (2112..2143
+// bits) take the CPU oracle.
 #include "kernels.h"
 
 #define WAVE 64
@@ -476,6 +478,17 @@ __global__ void k3_aggregate(
         }
     }
 
+    if constexpr (NDIG > 4) {
+        // 5 and 10 planes: the run-time bound below is no longer unrolled
+        // away, and racc[e] indexed by a loop counter would live in scratch
+        // for the whole kernel. Predicate a fully unrolled flush instead.
+#pragma unroll
+        for (int d = 0; d < NDIG; ++d)
+#pragma unroll
+            for (int e = 0; e < EPT; ++e)
+                if (e < nelem) acc[uint64_t(d) * len + e0 + e] += racc[e][d];
+        return;
+    }
 #pragma unroll
     for (int d = 0; d < NDIG; ++d) {
         for (int e = 0; e < nelem; ++e) {
@@ -974,6 +987,304 @@ extern "C" __global__ void k6_pack_u128(
     for (int b = 8; b < bpn; ++b) p[b] = uint8_t(hi >> (8 * (b - 8)));
 }
 
+// ------------------------------------------- multi-limb orders (up to 2^320)
+//
+// Group orders in [2^128, 2^320): the Bmax configs of f32 (289..320 bits,
+// bpn 37..40) and of i64 at M12 (138 bits, bpn 18). Canonical values are L =
+// ceil(bits/64) rows of u64 limbs; row j of a value tensor lives at
+// base + j*rstride (the bindings' (lo, hi) pair: base = lo, rstride = hi -
+// lo). Kernels are templated on L and keep a value in L (or L+1) register
+// pairs; the arithmetic is limbs.h. The accumulator stays u64-per-32-bit-digit
+// planes (5 or 10 of them), so K3 is the same kernel at more planes.
+
+template <int L>
+__device__ __forceinline__ limbs<L> ml_load(const uint64_t* __restrict__ base, int64_t rstride,
+                                            uint64_t i) {
+    limbs<L> v;
+#pragma unroll
+    for (int j = 0; j < L; ++j) v.w[j] = base[int64_t(j) * rstride + int64_t(i)];
+    return v;
+}
+
+template <int L>
+__device__ __forceinline__ void ml_store(uint64_t* __restrict__ base, int64_t rstride,
+                                         uint64_t i, const limbs<L>& v) {
+#pragma unroll
+    for (int j = 0; j < L; ++j) base[int64_t(j) * rstride + int64_t(i)] = v.w[j];
+}
+
+// K1a for multi-limb orders: k1_candidates_lds_u128 with draws of wpd =
+// ceil(nbytes/4) keystream words (5 for 18 bytes, 10 for 37..40), the top word
+// masked to nbytes, and an L-limb compare. Attempts per thread are 16/wpd
+// rounded down (3 or 1), so a workgroup's attempts span at most the 256
+// staged blocks (+1 boundary). Accepted draws compact in order into
+// per-workgroup segments (capacity 256*apt) of the L candidate planes, plane
+// j at cand + j*cstride. Acceptance is as low as 0.5%, so most workgroups
+// write nothing but their zero count.
+template <int L>
+__global__ void __launch_bounds__(K1_LDS_THREADS) k1_candidates_lds_ml(
+    const uint32_t* __restrict__ key8, uint64_t start_word, uint64_t first_attempt,
+    uint64_t n_attempts, int words_per_draw, int nbytes, xhip_limbs order_c,
+    uint64_t* __restrict__ cand, int64_t cstride, uint32_t* __restrict__ wg_counts,
+    int attempts_per_thread) {
+    __shared__ uint32_t lds_words[K1_LDS_THREADS * 16 + 16];
+    __shared__ uint32_t wave_tot[4];
+
+    uint32_t key[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) key[i] = key8[i];
+    const limbs<L> order = ml_from<L>(order_c);
+
+    const int apt = attempts_per_thread;
+    const int wpd = words_per_draw;
+    uint64_t A0 = first_attempt + uint64_t(blockIdx.x) * K1_LDS_THREADS * apt;
+    uint64_t W0 = start_word + A0 * uint64_t(wpd);
+    uint64_t first_blk = W0 >> 4;
+    int off0 = int(W0 & 15);
+    // blocks needed: ceil((off0 + 256*apt*wpd) / 16), <= 257 as apt*wpd <= 16
+    int need_blocks = (off0 + K1_LDS_THREADS * apt * wpd + 15) >> 4;
+
+    uint32_t tmp[16];
+    if (int(threadIdx.x) < need_blocks) {
+        chacha20_block_dev(key, first_blk + threadIdx.x, tmp);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) lds_words[(threadIdx.x << 4) + i] = tmp[i];
+    }
+    if (need_blocks > K1_LDS_THREADS && threadIdx.x == 0) {
+        chacha20_block_dev(key, first_blk + K1_LDS_THREADS, tmp);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) lds_words[(K1_LDS_THREADS << 4) + i] = tmp[i];
+    }
+    __syncthreads();
+
+    uint64_t a_rel0 = (uint64_t(blockIdx.x) * K1_LDS_THREADS + threadIdx.x) * apt;
+    int widx = off0 + int(threadIdx.x) * apt * wpd;
+    const int top_bytes = nbytes - 4 * (wpd - 1);  // valid bytes of the top word, 1..4
+    const uint32_t top_mask = top_bytes >= 4 ? 0xffffffffu : ((1u << (8 * top_bytes)) - 1);
+    // word k of draw d, zero beyond the draw, the top word masked
+    auto word = [&](int d, int k) -> uint64_t {
+        if (k >= wpd) return 0;
+        uint32_t x = lds_words[widx + d * wpd + k];
+        if (k == wpd - 1) x &= top_mask;
+        return uint64_t(x);
+    };
+    auto extract = [&](int d) {
+        limbs<L> v;
+#pragma unroll
+        for (int j = 0; j < L; ++j) v.w[j] = word(d, 2 * j) | (word(d, 2 * j + 1) << 32);
+        return v;
+    };
+    // bitmask + re-extract (see k1_candidates_lds)
+    uint32_t accept_bits = 0;
+    uint32_t mine = 0;
+    if (a_rel0 < n_attempts) {
+        for (int d = 0; d < apt; ++d) {
+            if (a_rel0 + d >= n_attempts) break;
+            if (!ml_geq(extract(d), order)) {
+                accept_bits |= 1u << d;
+                ++mine;
+            }
+        }
+    }
+    uint64_t k =
+        uint64_t(blockIdx.x) * K1_LDS_THREADS * apt + block_excl_scan<4>(mine, wave_tot);
+    while (accept_bits) {
+        int d = __builtin_ctz(accept_bits);
+        accept_bits &= accept_bits - 1;
+        ml_store<L>(cand, cstride, k, extract(d));
+        ++k;
+    }
+    if (threadIdx.x == K1_LDS_THREADS - 1)
+        wg_counts[blockIdx.x] = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
+}
+
+template <int L>
+__global__ void k1_scatter_compact_ml(
+    const uint64_t* __restrict__ cand, int64_t cstride,
+    const uint32_t* __restrict__ wg_offsets, const uint64_t* __restrict__ total,
+    uint32_t n_wgs, int per_wg_capacity, uint64_t out_base,
+    uint64_t* __restrict__ out, int64_t ostride, uint64_t out_len) {
+    uint32_t wg = blockIdx.x;
+    uint64_t beg = wg_offsets[wg];
+    uint64_t end = (wg + 1 < n_wgs) ? uint64_t(wg_offsets[wg + 1]) : *total;
+    uint64_t src = uint64_t(wg) * per_wg_capacity;
+    for (uint64_t i = threadIdx.x; i < end - beg; i += blockDim.x) {
+        uint64_t pos = out_base + beg + i;
+        if (pos < out_len) ml_store<L>(out, ostride, pos, ml_load<L>(cand, cstride, src + i));
+    }
+}
+
+// digit planes -> canonical limb rows mod order
+template <int L>
+__global__ void k2_canonicalize_ml(
+    const uint64_t* __restrict__ acc, uint64_t* __restrict__ out, int64_t ostride, uint64_t len,
+    int n_digits, int digit_bits, xhip_limbs order_c) {
+    uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= len) return;
+    limbs<L + 1> v = ml_from_planes<L + 1>(acc, len, i, n_digits, digit_bits);
+    ml_store<L>(out, ostride, i, ml_mod<L>(v, ml_from<L>(order_c)));
+}
+
+// The k digits (digit_bits wide, 1..63) of v, lowest first, through f(j,
+// digit): peel the low digit and shift, so no limb is picked by a run-time
+// index. Digits past the value's width are 0.
+template <int L, typename F>
+__device__ __forceinline__ void ml_for_digits(limbs<L> v, int k, int digit_bits, F f) {
+    const uint64_t digit_mask = (uint64_t(1) << digit_bits) - 1;
+    for (int j = 0; j < k; ++j) {
+        f(j, v.w[0] & digit_mask);
+        ml_shr_bits(v, digit_bits);
+    }
+}
+
+// canonical limb rows -> ADD into k planes of digit_bits-wide digits
+template <int L>
+__global__ void k_add_ml_to_planes(
+    uint64_t* __restrict__ planes, const uint64_t* __restrict__ vals, int64_t vstride,
+    uint64_t len, int k, int digit_bits) {
+    uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= len) return;
+    ml_for_digits<L>(ml_load<L>(vals, vstride, i), k, digit_bits,
+                     [&](int j, uint64_t digit) { planes[uint64_t(j) * len + i] += digit; });
+}
+
+// 32-bit accumulator planes -> value mod order -> WRITE k compact planes
+template <int L>
+__global__ void k2_recode_planes_ml(
+    const uint64_t* __restrict__ acc, uint64_t* __restrict__ out, uint64_t len, int n_digits,
+    xhip_limbs order_c, int k, int digit_bits) {
+    uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= len) return;
+    limbs<L + 1> v = ml_from_planes<L + 1>(acc, len, i, n_digits, 32);
+    ml_for_digits<L>(ml_mod<L>(v, ml_from<L>(order_c)), k, digit_bits,
+                     [&](int j, uint64_t digit) { out[uint64_t(j) * len + i] = digit; });
+}
+
+template <int L>
+__global__ void k2_mod_add_ml(
+    uint64_t* __restrict__ a, int64_t astride, const uint64_t* __restrict__ b, int64_t bstride,
+    uint64_t len, xhip_limbs order_c) {
+    uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= len) return;
+    limbs<L> av = ml_load<L>(a, astride, i);
+    ml_mod_add<L>(av, ml_load<L>(b, bstride, i), ml_from<L>(order_c));
+    ml_store<L>(a, astride, i, av);
+}
+
+// K6: wire limbs (bpn 17..40) <-> limb rows
+template <int L>
+__global__ void k6_unpack_ml(
+    const uint8_t* __restrict__ in, uint64_t* __restrict__ out, int64_t ostride, uint64_t len,
+    int bpn) {
+    uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= len) return;
+    const uint8_t* p = in + i * bpn;
+    limbs<L> v;
+#pragma unroll
+    for (int j = 0; j < L; ++j) {
+        uint64_t x = 0;
+#pragma unroll
+        for (int b = 0; b < 8; ++b)
+            if (8 * j + b < bpn) x |= uint64_t(p[8 * j + b]) << (8 * b);
+        v.w[j] = x;
+    }
+    ml_store<L>(out, ostride, i, v);
+}
+
+template <int L>
+__device__ __forceinline__ void ml_pack_bytes(uint8_t* __restrict__ p, int bpn,
+                                              const limbs<L>& v) {
+#pragma unroll
+    for (int j = 0; j < L; ++j)
+#pragma unroll
+        for (int b = 0; b < 8; ++b)
+            if (8 * j + b < bpn) p[8 * j + b] = uint8_t(v.w[j] >> (8 * b));
+}
+
+template <int L>
+__global__ void k6_pack_ml(
+    const uint64_t* __restrict__ in, int64_t istride, uint8_t* __restrict__ out, uint64_t len,
+    int bpn) {
+    uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= len) return;
+    ml_pack_bytes<L>(out + i * bpn, bpn, ml_load<L>(in, istride, i));
+}
+
+// K4 with an exact offset, for every Bmax config (L = 2..5). There n*add_shift
+// (up to nb * 2^128) dwarfs the weights it is subtracted from, so the
+// subtraction happens in integers:
+//   t = (planes mod order - mask) mod order,  d = t - C,  C = nb*add*E exact,
+// a signed multi-limb integer with weight = d / (E * scalar_sum).
+// Integer outputs (E = 10^10, one word): with `divisor` = E * scalar_sum as an
+// exact integer the truncated quotient |d| / divisor is exact; without one
+// (divisor == 0: it is no integer or exceeds a word) the double steps of
+// k4_unmask_u128 — q, r = divmod(|d|, E); (double(q) + double(r)/double(E))
+// signed, / scalar_sum, trunc.
+// Float outputs: |d| to double in one rounding, times scale = 1/(E *
+// scalar_sum), which the host forms in extended precision.
+template <typename OUT, bool TRUNC, int L>
+__global__ void k4_unmask_offset(
+    const uint64_t* __restrict__ planes, const uint64_t* __restrict__ mask, int64_t mstride,
+    OUT* __restrict__ out, uint64_t len, int n_planes, int digit_bits, xhip_limbs order_c,
+    xhip_limbs offset_c, uint64_t exp_word, uint64_t divisor, double scalar_sum, double scale) {
+    uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= len) return;
+    const limbs<L> order = ml_from<L>(order_c);
+    limbs<L + 1> v = ml_from_planes<L + 1>(planes, len, i, n_planes, digit_bits);
+    limbs<L> t = ml_mod_sub<L>(ml_mod<L>(v, order), ml_load<L>(mask, mstride, i), order);
+    limbs<L> mag = ml_from<L>(offset_c);  // |t - C|
+    bool neg = !ml_geq(t, mag);
+    if (neg) {
+        ml_sub(mag, t);
+    } else {
+        ml_sub(t, mag);
+        mag = t;
+    }
+    if constexpr (TRUNC) {
+        uint64_t r = ml_divrem_word(mag, divisor ? divisor : exp_word);  // mag = quotient
+        if (divisor) {
+            // two's-complement wrap of the low word, as the oracle's casts
+            uint64_t q = neg ? 0 - mag.w[0] : mag.w[0];
+            out[i] = OUT(int64_t(q));
+        } else {
+            double y = ml_to_double(mag) + double(r) / double(exp_word);
+            out[i] = OUT(trunc((neg ? -y : y) / scalar_sum));
+        }
+    } else {
+        double w = ml_to_double(mag) * scale;
+        out[i] = OUT(neg ? -w : w);
+    }
+}
+
+// K5w for Bmax configs: y = scalar * w (one double rounding, clamped to
+// +-add_shift), q = floor(y * E) through the exact mantissa mul-shift — for
+// negative y that is -ceil(|y| * E) — and the masked value add_shift*E + q +
+// mask mod order, all in integers: y + add_shift is never formed in floating
+// point, where add_shift (up to 2^128) would swallow y.
+template <typename T, int L>
+__global__ void k5_mask_weights_offset(
+    const T* __restrict__ w, const uint64_t* __restrict__ mask, int64_t mstride,
+    uint8_t* __restrict__ out, uint64_t len, int bpn, xhip_limbs order_c, double scalar,
+    double add_shift, xhip_limbs exp_c, xhip_limbs offset_c) {
+    uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= len) return;
+    const limbs<L> order = ml_from<L>(order_c);
+    double y = scalar * double(w[i]);
+    if (y > add_shift) y = add_shift;
+    if (y < -add_shift) y = -add_shift;
+    bool inexact;
+    limbs<L> q = ml_quantize<L>(y, ml_from<L>(exp_c), inexact);
+    limbs<L> val = ml_from<L>(offset_c);  // add_shift * E
+    if (y < 0.0) {
+        if (inexact) ml_add_word(q, 1);  // ceil
+        ml_sub(val, q);                  // |y| <= add_shift: stays >= 0
+    } else {
+        ml_add(val, q);  // <= 2*add_shift*E < order
+    }
+    ml_mod_add<L>(val, ml_load<L>(mask, mstride, i), order);
+    ml_pack_bytes<L>(out + i * bpn, bpn, val);
+}
+
 // ===================================================================
 // Host-side launchers (C ABI declared in kernels.h, consumed by
 // hip_bindings.cpp). All launches go to the null stream, which serializes
@@ -1137,6 +1448,12 @@ hipError_t xhip_k3_aggregate(uint64_t* acc, const uint8_t* updates, uint64_t str
         K3_CASE(14, 2, 4, 2)
         K3_CASE(15, 4, 4, 4)
         K3_CASE(16, 2, 4, 1)
+        // multi-limb Bmax configs: 5 (i64 M12) and 10 (f32) digit planes
+        K3_CASE(18, 2, 2, 2)
+        K3_CASE(37, 4, 4, 4)
+        K3_CASE(38, 2, 2, 2)
+        K3_CASE(39, 4, 4, 4)
+        K3_CASE(40, 2, 1, 2)
         default:
             return hipErrorInvalidValue;
     }
@@ -1260,3 +1577,213 @@ hipError_t xhip_k6_pack(const uint64_t* in_lo, const uint64_t* in_hi, uint8_t* o
     return launch_1d(k6_pack_u128, len, in_lo, in_hi, out, len, bpn);
 }
 
+// ---- every width: forward L <= 2, run the multi-limb kernels for L = 3..5 ----
+
+static int n_limbs_of(const xhip_limbs& v) {
+    int n = 1;
+    for (int j = 1; j < ML_MAX_LIMBS; ++j)
+        if (v.w[j]) n = j + 1;
+    return n;
+}
+
+template <int L>
+struct LimbCount {
+    static constexpr int value = L;
+};
+
+// Calls f(LimbCount<L>{}) for L = n in MIN..5.
+template <int MIN, typename F>
+static hipError_t dispatch_limbs(int n, F f) {
+    if (n < MIN) return hipErrorInvalidValue;
+    if constexpr (MIN <= 2) {
+        if (n == 2) return f(LimbCount<2>{});
+    }
+    switch (n) {
+        case 3: return f(LimbCount<3>{});
+        case 4: return f(LimbCount<4>{});
+        case 5: return f(LimbCount<5>{});
+        default: return hipErrorInvalidValue;
+    }
+}
+
+// Multi-limb plane windows: the recombined integer, top plane entry (a sum
+// below 2^64) included, must stay under the 2^(64*(L+1) - 1) that ml_mod takes.
+static bool bad_planes_ml(int n_limbs, int n_planes, int digit_bits) {
+    if (n_planes < 1 || digit_bits < 1 || digit_bits > 63) return true;
+    return int64_t(n_planes - 1) * digit_bits + 64 > 64 * (n_limbs + 1) - 1;
+}
+
+// element distance between limb rows 0 and 1
+static int64_t row_stride(const uint64_t* lo, const uint64_t* hi) { return hi - lo; }
+
+hipError_t xhip_k1_candidates_limbs(const uint32_t* key8_dev, uint64_t start_word,
+                                    uint64_t first_attempt, uint64_t n_attempts,
+                                    int words_per_draw, int nbytes, xhip_limbs order,
+                                    uint64_t* cand_lo, uint64_t* cand_hi, uint32_t* wg_counts,
+                                    int attempts_per_thread, uint32_t* n_wgs_out) {
+    const int n = n_limbs_of(order);
+    if (n <= 2)
+        return xhip_k1_candidates(key8_dev, start_word, first_attempt, n_attempts,
+                                  words_per_draw, nbytes, order.w[0], order.w[1], cand_lo,
+                                  cand_hi, wg_counts, attempts_per_thread, n_wgs_out);
+    if (words_per_draw != (nbytes + 3) / 4 || words_per_draw > 2 * n ||
+        attempts_per_thread < 1 || attempts_per_thread * words_per_draw > 16)
+        return hipErrorInvalidValue;
+    uint32_t wgs = ceil_div_u32(n_attempts, uint64_t(K1_LDS_THREADS) * attempts_per_thread);
+    *n_wgs_out = wgs;
+    if (wgs == 0) return hipSuccess;
+    return dispatch_limbs<3>(n, [&](auto l) {
+        constexpr int L = decltype(l)::value;
+        hipLaunchKernelGGL(k1_candidates_lds_ml<L>, dim3(wgs), dim3(K1_LDS_THREADS), 0, 0,
+                           key8_dev, start_word, first_attempt, n_attempts, words_per_draw,
+                           nbytes, order, cand_lo, row_stride(cand_lo, cand_hi), wg_counts,
+                           attempts_per_thread);
+        return hipGetLastError();
+    });
+}
+
+hipError_t xhip_k1_scatter_compact_limbs(const uint64_t* cand_lo, const uint64_t* cand_hi,
+                                         const uint32_t* wg_offsets, const uint64_t* total_dev,
+                                         uint32_t n_wgs, int apt, uint64_t out_base,
+                                         uint64_t* out_lo, uint64_t* out_hi, uint64_t out_len,
+                                         xhip_limbs order) {
+    const int n = n_limbs_of(order);
+    if (n <= 2)
+        return xhip_k1_scatter_compact(cand_lo, cand_hi, wg_offsets, total_dev, n_wgs, apt,
+                                       out_base, out_lo, out_hi, out_len);
+    if (n_wgs == 0) return hipSuccess;
+    return dispatch_limbs<3>(n, [&](auto l) {
+        constexpr int L = decltype(l)::value;
+        hipLaunchKernelGGL(k1_scatter_compact_ml<L>, dim3(n_wgs), dim3(256), 0, 0, cand_lo,
+                           row_stride(cand_lo, cand_hi), wg_offsets, total_dev, n_wgs, 256 * apt,
+                           out_base, out_lo, row_stride(out_lo, out_hi), out_len);
+        return hipGetLastError();
+    });
+}
+
+hipError_t xhip_k4_unmask_limbs(const uint64_t* planes, const uint64_t* mask_lo,
+                                const uint64_t* mask_hi, int dtype, void* out, uint64_t len,
+                                int n_planes, int digit_bits, xhip_limbs order,
+                                xhip_limbs exp_shift, double n_add_shift, double scalar_sum,
+                                xhip_limbs offset, uint64_t divisor, double scale) {
+    const int n = n_limbs_of(order);
+    const bool exact_offset = n_limbs_of(offset) > 1 || offset.w[0] != 0;
+    if (!exact_offset) {
+        if (n > 2 || n_limbs_of(exp_shift) > 2) return hipErrorInvalidValue;
+        return xhip_k4_unmask(planes, mask_lo, mask_hi, dtype, out, len, n_planes, digit_bits,
+                              order.w[0], order.w[1], exp_shift.w[0], exp_shift.w[1],
+                              n_add_shift, scalar_sum);
+    }
+    if (bad_planes_ml(n, n_planes, digit_bits) || n_limbs_of(offset) > n)
+        return hipErrorInvalidValue;
+    const bool exp_is_word = n_limbs_of(exp_shift) == 1 && exp_shift.w[0] != 0;
+    return dispatch_dtype(dtype, [&](auto t) {
+        using OUT = typename decltype(t)::type;
+        constexpr bool TRUNC = decltype(t)::trunc;
+        if (TRUNC && !exp_is_word) return hipErrorInvalidValue;
+        return dispatch_limbs<2>(n, [&](auto l) {
+            return launch_1d(k4_unmask_offset<OUT, TRUNC, decltype(l)::value>, len, planes,
+                             mask_lo, row_stride(mask_lo, mask_hi), static_cast<OUT*>(out), len,
+                             n_planes, digit_bits, order, offset, exp_shift.w[0], divisor,
+                             scalar_sum, scale);
+        });
+    });
+}
+
+hipError_t xhip_k2_canonicalize_limbs(const uint64_t* planes, uint64_t* out_lo,
+                                      uint64_t* out_hi, uint64_t len, int n_planes,
+                                      int digit_bits, xhip_limbs order) {
+    const int n = n_limbs_of(order);
+    if (n <= 2)
+        return xhip_k2_canonicalize(planes, out_lo, out_hi, len, n_planes, digit_bits,
+                                    order.w[0], order.w[1]);
+    if (bad_planes_ml(n, n_planes, digit_bits)) return hipErrorInvalidValue;
+    return dispatch_limbs<3>(n, [&](auto l) {
+        return launch_1d(k2_canonicalize_ml<decltype(l)::value>, len, planes, out_lo,
+                         row_stride(out_lo, out_hi), len, n_planes, digit_bits, order);
+    });
+}
+
+hipError_t xhip_add_to_planes_limbs(uint64_t* planes, const uint64_t* lo, const uint64_t* hi,
+                                    uint64_t len, int n_planes, int digit_bits,
+                                    xhip_limbs order) {
+    const int n = n_limbs_of(order);
+    if (n <= 2) return xhip_add_to_planes(planes, lo, hi, len, n_planes, digit_bits);
+    if (n_planes < 1 || digit_bits < 1 || digit_bits > 63) return hipErrorInvalidValue;
+    return dispatch_limbs<3>(n, [&](auto l) {
+        return launch_1d(k_add_ml_to_planes<decltype(l)::value>, len, planes, lo,
+                         row_stride(lo, hi), len, n_planes, digit_bits);
+    });
+}
+
+hipError_t xhip_k2_recode_planes_limbs(const uint64_t* acc, uint64_t* out, uint64_t len,
+                                       int n_digits, xhip_limbs order, int k, int digit_bits) {
+    const int n = n_limbs_of(order);
+    if (n <= 2)
+        return xhip_k2_recode_planes(acc, out, len, n_digits, order.w[0], order.w[1], k,
+                                     digit_bits);
+    if (bad_planes_ml(n, n_digits, 32) || k < 1 || digit_bits < 1 || digit_bits > 63)
+        return hipErrorInvalidValue;
+    return dispatch_limbs<3>(n, [&](auto l) {
+        return launch_1d(k2_recode_planes_ml<decltype(l)::value>, len, acc, out, len, n_digits,
+                         order, k, digit_bits);
+    });
+}
+
+hipError_t xhip_k2_mod_add_limbs(uint64_t* a_lo, uint64_t* a_hi, const uint64_t* b_lo,
+                                 const uint64_t* b_hi, uint64_t len, xhip_limbs order) {
+    const int n = n_limbs_of(order);
+    if (n <= 2) return xhip_k2_mod_add(a_lo, a_hi, b_lo, b_hi, len, order.w[0], order.w[1]);
+    return dispatch_limbs<3>(n, [&](auto l) {
+        return launch_1d(k2_mod_add_ml<decltype(l)::value>, len, a_lo, row_stride(a_lo, a_hi),
+                         b_lo, row_stride(b_lo, b_hi), len, order);
+    });
+}
+
+hipError_t xhip_k5_mask_weights_limbs(const void* w, int dtype, const uint64_t* mask_lo,
+                                      const uint64_t* mask_hi, uint8_t* out, uint64_t len,
+                                      int bpn, xhip_limbs order, double scalar, double add_shift,
+                                      xhip_limbs exp_shift, xhip_limbs offset) {
+    const int n = n_limbs_of(order);
+    const bool exact_offset = n_limbs_of(offset) > 1 || offset.w[0] != 0;
+    if (!exact_offset) {
+        if (n > 2 || n_limbs_of(exp_shift) > 2) return hipErrorInvalidValue;
+        return xhip_k5_mask_weights(w, dtype, mask_lo, mask_hi, out, len, bpn, order.w[0],
+                                    order.w[1], scalar, add_shift, exp_shift.w[0],
+                                    exp_shift.w[1]);
+    }
+    // 2^53 * exp_shift (the mantissa product) and the offset must fit L limbs
+    if (bpn < 1 || bpn > 8 * n || n_limbs_of(offset) > n || n_limbs_of(exp_shift) > n ||
+        exp_shift.w[n - 1] >> 11)
+        return hipErrorInvalidValue;
+    return dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        return dispatch_limbs<2>(n, [&](auto l) {
+            return launch_1d(k5_mask_weights_offset<T, decltype(l)::value>, len,
+                             static_cast<const T*>(w), mask_lo, row_stride(mask_lo, mask_hi),
+                             out, len, bpn, order, scalar, add_shift, exp_shift, offset);
+        });
+    });
+}
+
+hipError_t xhip_k6_unpack_limbs(const uint8_t* in, uint64_t* out_lo, uint64_t* out_hi,
+                                uint64_t len, int bpn, xhip_limbs order) {
+    const int n = n_limbs_of(order);
+    if (n <= 2) return xhip_k6_unpack(in, out_lo, out_hi, len, bpn);
+    if (bpn < 1 || bpn > 8 * n) return hipErrorInvalidValue;
+    return dispatch_limbs<3>(n, [&](auto l) {
+        return launch_1d(k6_unpack_ml<decltype(l)::value>, len, in, out_lo,
+                         row_stride(out_lo, out_hi), len, bpn);
+    });
+}
+
+hipError_t xhip_k6_pack_limbs(const uint64_t* in_lo, const uint64_t* in_hi, uint8_t* out,
+                              uint64_t len, int bpn, xhip_limbs order) {
+    const int n = n_limbs_of(order);
+    if (n <= 2) return xhip_k6_pack(in_lo, in_hi, out, len, bpn);
+    if (bpn < 1 || bpn > 8 * n) return hipErrorInvalidValue;
+    return dispatch_limbs<3>(n, [&](auto l) {
+        return launch_1d(k6_pack_ml<decltype(l)::value>, len, in_lo, row_stride(in_lo, in_hi),
+                         out, len, bpn);
+    });
+}

@@ -1,16 +1,35 @@
 """What the GPU engine and its CPU analog share: the config-derived fields,
 the update-pool layout, the exact CPU-side unit (scalar) arithmetic and the
 shape of canonical value tensors."""
+from fractions import Fraction
+
 import torch
 
 from xaynet_amd import _core
 
 
+MAX_BYTES_PER_NUMBER = 40  # group orders below 2^320: up to five u64 limbs
+
+# Bmax shifts per mask::DataType (csrc/mask/config.cpp, compute_exp_exponent
+# and compute_add_shift): the clamp bound is the data type's own extreme.
+_BMAX_SHIFTS = {
+    0: (10**45, (2**24 - 1) << 104),  # F32: f32::MAX
+    2: (10**10, 2**31),               # I32: -i32::MIN
+    3: (10**10, 2**63),               # I64: -i64::MIN
+}
+
+
 def _cfg_scalars(cfg):
-    """exp/add shifts as python scalars (non-Bmax configs)."""
-    exp_exp = {0: 10, 1: 20, 2: 10, 3: 10}[cfg.dtype]  # non-Bmax
+    """exp/add shifts as python scalars: floats (and the integer exp_shift)
+    for the B0..B6 bounds, exact ints for Bmax, whose add_shift * exp_shift
+    no double holds."""
     if cfg.bound == 255:
-        raise ValueError("Bmax configs are not on the u64 GPU path")
+        if cfg.dtype not in _BMAX_SHIFTS:
+            raise ValueError("F64 Bmax configs (2112..2143-bit orders) are not on the GPU "
+                             "path; use the CPU oracle for this config")
+        exp, add = _BMAX_SHIFTS[cfg.dtype]
+        return {"exp_shift": exp, "exp_shift_u64": exp, "add_shift": add}
+    exp_exp = {0: 10, 1: 20, 2: 10, 3: 10}[cfg.dtype]
     add = {0: 1.0, 2: 100.0, 4: 10_000.0, 6: 1_000_000.0}[cfg.bound]
     return {
         "exp_shift": float(10**exp_exp),
@@ -26,9 +45,9 @@ class MaskedAggregatorBase:
     _TORCH_DTYPES = {0: torch.float32, 1: torch.float64, 2: torch.int32, 3: torch.int64}
 
     def __init__(self, vect_cfg, unit_cfg, length: int, device):
-        if vect_cfg.bytes_per_number > 16:
+        if vect_cfg.bytes_per_number > MAX_BYTES_PER_NUMBER:
             raise ValueError(
-                f"{type(self).__name__} covers group orders up to 2^128 (got "
+                f"{type(self).__name__} covers group orders up to 2^320 (got "
                 f"{vect_cfg.bytes_per_number} bytes/element); use the CPU oracle for this config"
             )
         self.vect_cfg = vect_cfg
@@ -36,9 +55,11 @@ class MaskedAggregatorBase:
         self.length = length
         self.device = torch.device(device)
         self.bpn = vect_cfg.bytes_per_number
-        # wide (order >= 2^64) configs: canonical values are split lo/hi u64
-        # rows, [2, n]; u64 orders: [n]
+        # wide (order >= 2^64) configs: canonical values are rows of u64
+        # limbs, [n_limbs, n] (lo/hi for orders up to 2^128); u64 orders: [n]
         self.wide = not vect_cfg.order_fits_u64
+        self.n_limbs = (int(vect_cfg.order).bit_length() + 63) // 64
+        self.bmax = vect_cfg.bound == 255
         self.n_digits = (self.bpn + 3) // 4
         self.order = vect_cfg.order  # decimal string
         self.order_int = int(vect_cfg.order)
@@ -54,9 +75,10 @@ class MaskedAggregatorBase:
 
     def new_values(self, n: int | None = None, zero: bool = False) -> torch.Tensor:
         """A canonical value tensor for n (default: length) elements: int64
-        [n], or [2, n] lo/hi rows when the order is wide."""
+        [n], or [n_limbs, n] limb rows (lo/hi for orders up to 2^128) when the
+        order is wide."""
         n = self.length if n is None else n
-        shape = (2, n) if self.wide else (n,)
+        shape = (self.n_limbs, n) if self.wide else (n,)
         make = torch.zeros if zero else torch.empty
         return make(*shape, dtype=torch.int64, device=self.device)
 
@@ -87,20 +109,44 @@ class MaskedAggregatorBase:
     def masked_unit_for(self, seed: bytes, scalar_num: int, scalar_den: int) -> int:
         """Masked scalar for a synthetic update."""
         info = _cfg_scalars(self.unit_cfg)
-        exp = int(info["exp_shift"])
+        exp = int(info["exp_shift_u64"])
         add = int(info["add_shift"])
-        # trunc((clamp(scalar)+add)*exp): scalar = num/den <= add by protocol
+        # trunc((clamp(scalar)+add)*exp) in exact integers (Bmax shifts
+        # included): scalar = num/den <= add by protocol
         shifted = ((scalar_num + add * scalar_den) * exp) // scalar_den
         return (shifted + self.unit_draw(seed)) % int(self.unit_cfg.order)
 
     def _unmask_scalars(self, mask_unit: int, nb: int, dtype: int | None = None):
         """What every unmask needs besides the tensors: scalar_sum =
         n1/exp_1 - nb*add_1, the vect config's shifts, and the output
-        mask::DataType (default: the vect config's)."""
+        mask::DataType (default: the vect config's). A Bmax unit config has
+        nb*add_1 beyond the doubles that n1/exp_1 cancels against, so its
+        scalar_sum = (n1 - nb*add_1*exp_1)/exp_1 is formed exactly and rounded
+        once. For a Bmax vect config the shifts carry the exact integer
+        "offset" = nb * add_shift * exp_shift that the unmask subtracts in
+        the integer domain (None otherwise), and the "divisor": with d the
+        offset-free integer, a weight is d / (exp_shift * scalar_sum) =
+        d / divisor, divisor = exp_shift * (n1 - nb*add_1*exp_1) / exp_1.
+        Integer outputs truncate that quotient, which doubles cannot decide
+        beyond ~2^40, so the divisor is handed on as an exact integer where
+        it is one and fits a u64 (the same config for both parts and scalars
+        summing to less than 2^64 / exp_shift); None otherwise."""
         info = _cfg_scalars(self.unit_cfg)
         n1 = (self.unit_acc + int(self.unit_cfg.order) - mask_unit) % int(self.unit_cfg.order)
-        scalar_sum = n1 / info["exp_shift"] - nb * info["add_shift"]
+        exp1 = info["exp_shift_u64"]
+        if self.unit_cfg.bound == 255:
+            scalar_sum = float(Fraction(n1 - nb * info["add_shift"] * exp1, exp1))
+        else:
+            scalar_sum = n1 / info["exp_shift"] - nb * info["add_shift"]
         if scalar_sum == 0:
             raise ZeroDivisionError("scalar_sum is zero")
         dt = self.vect_cfg.dtype if dtype is None else dtype
-        return scalar_sum, _cfg_scalars(self.vect_cfg), dt
+        vinfo = _cfg_scalars(self.vect_cfg)
+        vinfo["offset"] = vinfo["divisor"] = None
+        if self.bmax:
+            vinfo["offset"] = nb * vinfo["add_shift"] * vinfo["exp_shift_u64"]
+            div = Fraction(vinfo["exp_shift_u64"] * (n1 - nb * int(info["add_shift"]) * exp1),
+                           exp1)
+            if div.denominator == 1 and 0 < div < 2**64:
+                vinfo["divisor"] = int(div)
+        return scalar_sum, vinfo, dt

@@ -6,11 +6,11 @@ plane and the gloo world>1 tests can run the EXACT same composition code
 without a GPU. Production deployments use the HIP engine; this class exists
 so the distributed path is provable in CPU CI.
 
-u64 orders use vectorised numpy u64 math. Wide orders (2^64 <= order <=
-2^128, bpn 9..16) use the GPU engine's layouts — canonical values as
-[2, length] lo/hi int64 tensors, compact digit planes of `digit_bits`-wide
-digits — and Python-int/object math internally: a test vehicle, not a hot
-path.
+u64 orders use vectorised numpy u64 math. Wide orders (2^64 <= order <
+2^320, bpn 9..40) use the GPU engine's layouts — canonical values as
+[n_limbs, length] int64 rows of u64 limbs (lo/hi up to 2^128), compact digit
+planes of `digit_bits`-wide digits — and Python-int/object math internally: a
+test vehicle, not a hot path.
 
 Semantics are pinned to the reference math (masking.rs:190-231, 292-316):
 plane arithmetic is the same deferred-modular scheme as kernels.hip, and the
@@ -18,6 +18,9 @@ unmask formula matches the K4 kernels (including their float order of
 operations) so CPU- and GPU-plane results agree on integer dtypes.
 """
 from __future__ import annotations
+
+import math
+from fractions import Fraction
 
 import numpy as np
 import torch
@@ -28,6 +31,15 @@ from .base import MaskedAggregatorBase
 
 _U64 = np.uint64
 _M64 = (1 << 64) - 1
+
+
+def _bmax_int_weight(d: int, exp: int, scalar_sum: float) -> float:
+    """Integer-dtype weight from the signed offset-free value d, in the
+    exact-offset K4's order of operations: exact quotient and remainder of
+    |d| by E, double(q) + double(r)/double(E), sign, / scalar_sum."""
+    q, r = divmod(abs(d), exp)
+    y = float(q) + float(r) / float(exp)
+    return (-y if d < 0 else y) / scalar_sum
 
 
 class CpuPlaneAggregator(MaskedAggregatorBase):
@@ -41,19 +53,21 @@ class CpuPlaneAggregator(MaskedAggregatorBase):
     # ---------------- value tensors <-> python ints ----------------
 
     def _ints(self, vals: torch.Tensor) -> np.ndarray:
-        """Canonical value tensor ([n], or wide [2, n] lo/hi) -> object ints."""
+        """Canonical value tensor ([n], or wide [n_limbs, n] limb rows) ->
+        object ints."""
         if self.wide:
-            lo = vals[0].numpy().view(_U64).astype(object)
-            hi = vals[1].numpy().view(_U64).astype(object)
-            return (hi << 64) + lo
+            total = np.zeros(vals.shape[1], dtype=object)
+            for j in reversed(range(vals.shape[0])):
+                total = (total << 64) + vals[j].numpy().view(_U64).astype(object)
+            return total
         return vals.numpy().view(_U64).astype(object)
 
     def _values(self, ints: np.ndarray) -> torch.Tensor:
         """Object ints -> canonical value tensor (inverse of _ints)."""
         if self.wide:
-            lo = np.array([int(v) & _M64 for v in ints], dtype=_U64)
-            hi = np.array([int(v) >> 64 for v in ints], dtype=_U64)
-            return torch.from_numpy(np.stack([lo, hi]).astype(np.int64))
+            rows = [np.array([(int(v) >> (64 * j)) & _M64 for v in ints], dtype=_U64)
+                    for j in range(self.n_limbs)]
+            return torch.from_numpy(np.stack(rows).astype(np.int64))
         return torch.from_numpy(np.array([int(v) for v in ints], dtype=_U64).astype(np.int64))
 
     @staticmethod
@@ -82,7 +96,8 @@ class CpuPlaneAggregator(MaskedAggregatorBase):
         """uint8 [length, bpn] -> canonical value tensor."""
         lo = self._limb_word(limbs, 0, 8)
         if self.wide:
-            lo = np.stack([lo, self._limb_word(limbs, 8, 16)])
+            lo = np.stack([lo] + [self._limb_word(limbs, 8 * j, 8 * j + 8)
+                                  for j in range(1, self.n_limbs)])
         return torch.from_numpy(lo.astype(np.int64))
 
     def unpack_wire(self, packed: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
@@ -90,7 +105,7 @@ class CpuPlaneAggregator(MaskedAggregatorBase):
         return self._ret(self._limbs_to_tensor(limbs), out)
 
     def pack_wire(self, values: torch.Tensor) -> torch.Tensor:
-        words = values.numpy().view(_U64).reshape(-1, self.length)  # [1 or 2, length]
+        words = values.numpy().view(_U64).reshape(-1, self.length)  # [n_limbs, length]
         out = np.zeros(self.length * self.bpn, dtype=np.uint8)
         limbs = out.reshape(self.length, self.bpn)
         for b in range(self.bpn):
@@ -191,7 +206,24 @@ class CpuPlaneAggregator(MaskedAggregatorBase):
         t = (masked + order - self._ints(mask_values)) % order
         exp = vinfo["exp_shift_u64"]
         n_add = nb * vinfo["add_shift"]
-        if self.wide:
+        if self.bmax:
+            # mirror the exact-offset K4: d = t - nb*add*E as a signed
+            # integer, then the same double steps as the kernel
+            d = [int(v) - vinfo["offset"] for v in t]
+            if dt in (2, 3) and vinfo["divisor"]:
+                # exact truncated quotient, never through doubles
+                div = vinfo["divisor"]
+                exact = [-(-v // div) if v < 0 else v // div for v in d]
+                return torch.from_numpy(np.array(exact, dtype=np.int64)
+                                        .astype(self._NP_DTYPES[dt]))
+            if dt in (2, 3):
+                outf = np.array([_bmax_int_weight(v, exp, scalar_sum) for v in d],
+                                dtype=np.float64)
+            else:
+                scale = float(1 / (exp * Fraction(scalar_sum)))
+                outf = np.array([math.copysign(float(abs(v)) * scale, v) for v in d],
+                                dtype=np.float64)
+        elif self.wide:
             # mirror k4_unmask_u128: double(t / E) + double(t % E) / double(E)
             outf = np.array([(float(int(v) // exp) + float(int(v) % exp) / float(exp) - n_add)
                              / scalar_sum for v in t], dtype=np.float64)

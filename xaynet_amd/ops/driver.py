@@ -10,9 +10,10 @@ This replaces the reference's in-RAM `Aggregation::aggregate` hot loop
 (rust/xaynet-core/src/mask/masking.rs:292-316) with the GPU engine while the
 protocol thread stays untouched (SURVEY.md §2.6 K3/K4/K6 mapping).
 
-All F32/F64/I32/I64 configs with group orders up to 2^128 are supported
-(every BASELINE.json config, plus the F64 wide-order families via the u128
-kernel set); only Bmax orders beyond 2^128 take the CPU oracle plane.
+All F32/F64/I32/I64 configs with group orders below 2^320 are supported
+(every BASELINE.json config, the F64 wide-order families via the u128 kernel
+set, the F32/I32/I64 Bmax configs via the exact-offset unmask and the
+multi-limb kernel set); only F64 Bmax takes the CPU oracle plane.
 """
 from __future__ import annotations
 

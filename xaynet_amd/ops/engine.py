@@ -7,19 +7,20 @@ Data layout (see csrc/gpu/kernels.hip):
     (plain integer sums; modular reduction deferred to finalize — this is
     what makes cross-GPU RCCL int64 all-reduce valid)
   - canonical values (masks, finalized sums): int64 [n] for orders < 2^64,
-    split lo/hi rows [2, n] for wide orders (`new_values`)
+    [n_limbs, n] rows of u64 limbs for wide orders: lo/hi rows [2, n] up to
+    2^128, 3..5 rows for the f32 and i64 Bmax orders (`new_values`)
 
 Every method hands `_hip` the values as a (lo, hi) pointer pair and the order
-as a decimal string; the extension picks the u64 or the u128 kernel from the
-order. Lengths come from the tensors, so every value/plane method also works
-on a shard.
+as a decimal string; the extension picks the u64, the u128 or the multi-limb
+kernel from the order. Lengths come from the tensors, so every value/plane
+method also works on a shard.
 
 Memory is owned by torch (device tensors); kernels launch on the null
 stream, which serializes with torch's default stream.
 
 Fails loudly if the _hip extension or a GPU is unavailable — there is no
-silent CPU fallback on a GPU box. Orders up to 2^128 are supported; only
-Bmax orders beyond 2^128 are routed to the CPU oracle by the caller.
+silent CPU fallback on a GPU box. Orders below 2^320 are supported; only the
+f64 Bmax orders (2112..2143 bits) are routed to the CPU oracle by the caller.
 """
 import os
 
@@ -64,13 +65,15 @@ class GpuMaskedAggregator(MaskedAggregatorBase):
 
     def _vals(self, t: torch.Tensor):
         """Canonical value tensor -> (lo_ptr, hi_ptr, n), the form every
-        `_hip` call takes: int64 [n] (hi_ptr 0) for u64 orders, [2, n] lo/hi
-        rows for wide ones. Rows must be dense; a column slice t[:, a:b] of a
-        [2, n] tensor is."""
+        `_hip` call takes: int64 [n] (hi_ptr 0) for u64 orders, [n_limbs, n]
+        limb rows for wide ones (lo/hi up to 2^128). lo and hi point at rows 0
+        and 1; the extension finds row j at lo + j*(hi - lo) and takes the row
+        count from the order. Rows must be dense; a column slice t[:, a:b] of
+        an [n_limbs, n] tensor is."""
         if t.dtype != torch.int64 or t.dim() != 1 + self.wide or t.stride(-1) != 1 \
-                or (self.wide and t.shape[0] != 2):
+                or (self.wide and t.shape[0] != self.n_limbs):
             raise ValueError("canonical values must be " + (
-                "[2, n] int64 lo/hi rows" if self.wide else "an [n] int64 tensor")
+                f"[{self.n_limbs}, n] int64 limb rows" if self.wide else "an [n] int64 tensor")
                 + " with unit element stride")
         if self.wide:
             return t[0].data_ptr(), t[1].data_ptr(), t.shape[1]
@@ -190,6 +193,13 @@ class GpuMaskedAggregator(MaskedAggregatorBase):
         ptr, k = self._planes(planes, n)
         scalar_sum, vinfo, dt = self._unmask_scalars(mask_unit, nb_models, dtype)
         out = torch.empty(n, dtype=self._TORCH_DTYPES[dt], device=planes.device)
+        if self.bmax:
+            # nb*add_shift is subtracted as the exact integer offset, not as
+            # a double (which the weights would vanish against)
+            _hip.unmask(ptr, lo, hi, out.data_ptr(), n, k, self.order,
+                        str(vinfo["exp_shift_u64"]), 0.0, scalar_sum, dt, digit_bits,
+                        offset=str(vinfo["offset"]), divisor=str(vinfo["divisor"] or ""))
+            return out
         _hip.unmask(ptr, lo, hi, out.data_ptr(), n, k, self.order, str(vinfo["exp_shift_u64"]),
                     nb_models * vinfo["add_shift"], scalar_sum, dt, digit_bits)
         return out
@@ -198,6 +208,10 @@ class GpuMaskedAggregator(MaskedAggregatorBase):
 
     def synth_update(self, pool: torch.Tensor, row: int, mask_values: torch.Tensor,
                      participant: int, scalar: float):
+        if self.bmax:
+            raise NotImplementedError(
+                "synthetic update rows (K5, benchmark only) do not cover Bmax configs; "
+                "mask real weights with mask_weights or the CPU masker")
         lo, hi, n = self._vals(mask_values)
         if n * self.bpn > pool.shape[1]:
             raise ValueError("synth_update: mask values longer than a pool row")
@@ -221,9 +235,12 @@ class GpuMaskedAggregator(MaskedAggregatorBase):
         lo, hi, n = self._vals(mask_vals)
         vinfo = _cfg_scalars(self.vect_cfg)
         out = torch.empty(n * self.bpn, dtype=torch.uint8, device=self.device)
+        # Bmax: add_shift (a dtype extreme, exact as a double) clamps; the
+        # shift itself is added as the integer add_shift * exp_shift
+        offset = str(vinfo["add_shift"] * vinfo["exp_shift_u64"]) if self.bmax else ""
         _hip.mask_weights(w_dev.data_ptr(), dt, lo, hi, out.data_ptr(), n, self.bpn, self.order,
-                          scalar_num / scalar_den, vinfo["add_shift"],
-                          str(vinfo["exp_shift_u64"]))
+                          scalar_num / scalar_den, float(vinfo["add_shift"]),
+                          str(vinfo["exp_shift_u64"]), offset=offset)
         # masked unit (scalar clamp + quantize + unit mask), exact on CPU
         return self.wire_object(out, self.masked_unit_for(seed, scalar_num, scalar_den))
 

@@ -8,8 +8,9 @@ MaskObject wire bytes the coordinator expects — bit-identical to the CPU
 oracle (the K1 compaction reproduces the reference's sequential rejection
 stream).
 
-All orders up to 2^128 (u64 fast path + split lo/hi u128 kernels); only
-Bmax orders beyond 2^128 stay on the CPU path.
+All orders below 2^320 (u64 fast path, split lo/hi u128 kernels, multi-limb
+kernels for the f32 and i64 Bmax orders); only the f64 Bmax orders stay on the
+CPU path.
 """
 from __future__ import annotations
 

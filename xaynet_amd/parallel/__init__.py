@@ -16,7 +16,9 @@ Wide orders (2^64 <= order <= 2^128) carry 3-4 accumulator planes (24-32 B
 per element). Their reduce-scatter re-digitises the locally canonicalised
 value into the fewest digit planes that still leave headroom for the
 cross-rank sum (`compact_digits`): 2 planes up to 120-bit orders, 3 beyond —
-16 or 24 B per element on the wire.
+16 or 24 B per element on the wire. The multi-limb Bmax orders (138..320
+bits, 5 or 10 accumulator planes) take the same path with more planes: 3 at
+138 bits, 5 or 6 at 289..320.
 
 `bench.py` and the multi-GPU serve plane both drive their timed N>1 path
 through this module, so the benchmark measures the production code;
@@ -90,7 +92,8 @@ class ShardedAggregation:
 
     `mask_total` must be the GLOBAL canonical mask values (same on every
     rank — use `allreduce_mask` to combine per-rank partial mask sums).
-    Wide (u128) orders pass the [2, length] lo/hi split the engine uses.
+    Wide orders pass the [n_limbs, length] limb rows the engine uses ([2,
+    length] lo/hi up to 2^128).
     """
 
     def __init__(self, eng, dist, rank: int, world: int):
@@ -102,6 +105,8 @@ class ShardedAggregation:
         self._shard = eng.length // world if self.strategy.endswith("_rs") else eng.length
         # wide orders: (plane count, digit width) of the compact cross-rank planes
         self._digits = compact_digits(eng.order_int, world) if eng.wide else None
+        if self._digits is not None:  # the int64 collective cannot overflow
+            assert world * (2**self._digits[1] - 1) < 2**63
         self._buf = {}  # persistent scratch (steady-state rounds reuse them)
 
     def _scratch(self, name: str, *shape, dtype=torch.int64):

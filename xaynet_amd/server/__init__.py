@@ -78,12 +78,16 @@ def serve(settings: Settings, ready_event: threading.Event | None = None,
 
     driver = None
     if settings.gpu:
+        from xaynet_amd.ops.base import MAX_BYTES_PER_NUMBER
+
         c = _core.mask.MaskConfig(*settings.mask_config_args())
-        if c.bytes_per_number > 16:
+        if c.bytes_per_number > MAX_BYTES_PER_NUMBER:
+            # only F64 Bmax: 2112..2143-bit orders
             LOG.warning(
-                "mask config %s has a group order wider than 128 bits; the GPU "
-                "data plane covers orders up to 2^128 — using the CPU "
-                "aggregation plane for this deployment", settings.mask.data_type)
+                "mask config %s/Bmax has a %d-bit group order; the GPU data plane "
+                "covers orders below 2^320 (every config but F64 Bmax) — using the "
+                "CPU aggregation plane for this deployment",
+                settings.mask.data_type, int(c.order).bit_length())
             settings.gpu = False
     coordinator, store, models = build_coordinator(settings)
     if settings.gpu:
