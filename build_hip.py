@@ -21,7 +21,8 @@ def build(verbose=True):
     out = os.path.join(root, "xaynet_amd", f"_hip{ext}")
 
     # skip if up to date (kernels.h: the C ABI both sources include)
-    deps = src + [os.path.join(root, "xaynet_amd", "csrc", "gpu", h) for h in ("kernels.h", "limbs.h")]
+    deps = src + [os.path.join(root, "xaynet_amd", "csrc", "gpu", h) for h in ("kernels.h", "limbs.h", "k1_candidates_lds_body.inc",
+                        "k1_candidates_lds_u128_body.inc")]
     if os.path.exists(out) and all(os.path.getmtime(out) > os.path.getmtime(s) for s in deps):
         if verbose:
             print(f"_hip up to date: {out}")

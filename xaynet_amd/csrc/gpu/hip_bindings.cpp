@@ -5,10 +5,14 @@
 // stream on the device.
 #include <pybind11/pybind11.h>
 
+#include <pybind11/stl.h>
+
 #include <cmath>
+#include <cstring>
 #include <stdexcept>
 #include <string>
 #include <utility>
+#include <vector>
 
 #include "kernels.h"
 
@@ -126,48 +130,157 @@ class DeviceBuffer {
 // (computed on CPU via _core.mask.unit_draw).
 class MaskExpander {
   public:
-    // Size a launch for the elements still missing at the acceptance
-    // probability, run candidates -> scan -> scatter, read back the accepted
-    // count, repeat until `len` are filled. Returns the number of draw
-    // ATTEMPTS launched. That is NOT the stream position of the len-th
-    // acceptance (the last launch overshoots); a caller needing that position
-    // should account on the CPU. Masks are always derived from a fresh seed,
-    // so the protocol never uses the tail position.
-    uint64_t expand(const std::string& seed, uintptr_t out_lo_ptr, uintptr_t out_hi_ptr,
-                    uint64_t len, const std::string& order_dec, int prng_nbytes,
-                    uint64_t start_word) {
-        const Limbs order = parse_order(order_dec, out_hi_ptr);
+    // The sizes of one seed's first launch, and with them the batch rule.
+    struct Plan {
+        int wpd;          // keystream words per attempt: 1..10
+        int apt;          // attempts per candidates thread (workgroups cover 256 * apt)
+        double p;         // acceptance probability
+        uint64_t n_att;   // attempts of the first launch
+        uint64_t wgs;     // its candidate workgroups
+        bool batchable;   // seeds may share a launch
+    };
+
+    // attempts == 0: size the launch for `remaining` elements at the
+    // acceptance probability (+6 sigma). Seeds are expanded together only for
+    // u64 and u128 orders and only while one seed's launch stays within the
+    // single-workgroup scan (XHIP_K1_SCAN_ONE_WG candidate workgroups); this
+    // is the one place that decides it.
+    static Plan plan(const Limbs& order, int prng_nbytes, uint64_t remaining, uint64_t attempts) {
+        Plan pl;
         const int L = order.n;
-        if (seed.size() != 32) throw py::value_error("seed must be 32 bytes");
+        pl.wpd = (prng_nbytes + 3) / 4;
+        pl.apt = 16 / pl.wpd;
+        const double order_d =
+            L <= 2 ? double(order.v.w[1]) * 18446744073709551616.0 + double(order.v.w[0])
+                   : double(limbs_to_ld(order));
+        pl.p = order_d * std::pow(2.0, -8.0 * prng_nbytes);
+        const double exp_att = double(remaining) / pl.p;
+        pl.n_att = attempts ? attempts
+                            : uint64_t(exp_att + 6.0 * std::sqrt(exp_att / pl.p) + 1024.0);
+        // multi-limb orders accept as few as 1 draw in 200: cap the launch
+        // so the workspace does not grow with 1/p, and loop
+        if (L > 2 && pl.n_att > kMaxAttemptsPerLaunch) pl.n_att = kMaxAttemptsPerLaunch;
+        pl.wgs = (pl.n_att + 256 * pl.apt - 1) / (256 * pl.apt);
+        pl.batchable = L <= 2 && pl.wgs <= XHIP_K1_SCAN_ONE_WG;
+        return pl;
+    }
+
+    static void check_nbytes(const Limbs& order, int prng_nbytes) {
+        const int L = order.n;
         const int lo_bytes = L == 1 ? 1 : L == 2 ? 9 : 17, hi_bytes = L <= 2 ? 8 * L : 40;
         if (prng_nbytes < lo_bytes || prng_nbytes > hi_bytes || prng_nbytes > 8 * L)
             throw py::value_error(
                 "prng_nbytes must be 1..8 for u64 orders, 9..16 for u128, 17..40 beyond");
+    }
+
+    // How many seeds one expand() call should carry for masks of `len`
+    // elements: as many as keep the value rows and the candidate planes of a
+    // batch within budget_bytes, at most XHIP_K1_MAX_BATCH, and 1 where the
+    // batch rule (plan) says so.
+    static uint64_t batch_size(uint64_t len, const std::string& order_dec, int prng_nbytes,
+                               uint64_t budget_bytes) {
+        const Limbs order = parse_limbs(order_dec);
+        check_nbytes(order, prng_nbytes);
+        if (len == 0) return 1;
+        const Plan pl = plan(order, prng_nbytes, len, 0);
+        if (!pl.batchable) return 1;
+        const uint64_t per_seed = 8 * uint64_t(order.n) * (len + pl.wgs * 256 * pl.apt);
+        uint64_t b = budget_bytes / per_seed;
+        if (b > XHIP_K1_MAX_BATCH) b = XHIP_K1_MAX_BATCH;
+        return b < 1 ? 1 : b;
+    }
+
+    // Expand S = seeds.size()/32 seeds; seed s fills out_lo/out_hi +
+    // s*seed_stride with `len` mask values. Each seed's launch is sized for
+    // the missing elements at the acceptance probability (or `attempts`, the
+    // first time), runs candidates -> scan -> scatter, reads back the
+    // accepted count, and repeats until `len` are filled. Seeds that may
+    // share a launch (plan) take their first launch together: one copy of
+    // keys and start words in, one copy of S accepted counts out; a seed that
+    // falls short is finished by the single-seed loop from where the batch
+    // left it. Returns the number of draw ATTEMPTS launched. That is NOT the
+    // stream position of the len-th acceptance (the last launch overshoots);
+    // a caller needing that position should account on the CPU. Masks are
+    // always derived from a fresh seed, so the protocol never uses the tail
+    // position.
+    uint64_t expand(const std::string& seeds, uintptr_t out_lo_ptr, uintptr_t out_hi_ptr,
+                    uint64_t len, const std::string& order_dec, int prng_nbytes,
+                    const std::vector<uint64_t>& start_words, uint64_t seed_stride,
+                    uint64_t attempts) {
+        const Limbs order = parse_order(order_dec, out_hi_ptr);
+        const uint64_t S = seeds.size() / 32;
+        if (seeds.empty() || seeds.size() % 32) throw py::value_error("seed must be 32*S bytes");
+        if (S > XHIP_K1_MAX_BATCH) throw py::value_error("at most 65535 seeds per call");
+        if (start_words.size() != S) throw py::value_error("one start_word per seed");
+        if (S > 1 && (seed_stride == 0 || seed_stride < len))
+            throw py::value_error("several seeds need seed_stride, the u64 elements between "
+                                  "their outputs (at least len)");
+        check_nbytes(order, prng_nbytes);
         if (len == 0) return 0;
-        const int wpd = (prng_nbytes + 3) / 4;  // keystream words per attempt: 1..10
-        const int apt = 16 / wpd;  // attempts per candidates thread (workgroups cover 256 * apt)
-        const double order_d =
-            L <= 2 ? double(order.v.w[1]) * 18446744073709551616.0 + double(order.v.w[0])
-                   : double(limbs_to_ld(order));
-        const double p = order_d * std::pow(2.0, -8.0 * prng_nbytes);  // acceptance
         uint64_t* out_lo = u64p(out_lo_ptr);
         uint64_t* out_hi = u64p(out_hi_ptr);
 
-        key_.reserve(8, "alloc key");
-        total_.reserve(1, "alloc total");
-        check(hipMemcpy(key_.get(), seed.data(), 32, hipMemcpyHostToDevice), "seed H2D");
+        // keys, then the start words, in one buffer and one copy
+        std::vector<uint32_t> staging(10 * S);
+        std::memcpy(staging.data(), seeds.data(), 32 * S);
+        std::memcpy(staging.data() + 8 * S, start_words.data(), 8 * S);
+        key_.reserve(10 * S, "alloc keys");
+        check(hipMemcpy(key_.get(), staging.data(), 40 * S, hipMemcpyHostToDevice), "seed H2D");
 
-        uint64_t filled = 0, attempt = 0;
+        const Plan pl = plan(order, prng_nbytes, len, attempts);
+        if (S == 1 || !pl.batchable) {
+            uint64_t launched = 0;
+            for (uint64_t s = 0; s < S; ++s)
+                launched += finish(key_.get() + 8 * s, start_words[s], out_lo + s * seed_stride,
+                                   out_hi ? out_hi + s * seed_stride : nullptr, len, order,
+                                   prng_nbytes, 0, 0, attempts);
+            return launched;
+        }
+
+        const uint64_t cand_stride = pl.wgs * 256 * pl.apt;
+        const uint32_t counts_stride = uint32_t(pl.wgs);
+        cand_lo_.reserve(S * cand_stride, "alloc cand");
+        if (order.n == 2) cand_hi_.reserve(S * cand_stride, "alloc cand_hi");
+        counts_.reserve(S * counts_stride, "alloc counts");
+        total_.reserve(S, "alloc totals");
+        check(xhip_k1_expand_batch(
+                  key_.get(), reinterpret_cast<const uint64_t*>(key_.get() + 8 * S), uint32_t(S),
+                  pl.n_att, pl.wpd, prng_nbytes, order.v.w[0], order.v.w[1], cand_lo_.get(),
+                  order.n == 2 ? cand_hi_.get() : nullptr, cand_stride, counts_.get(),
+                  counts_stride, total_.get(), pl.apt, out_lo, out_hi, seed_stride, len),
+              "k1_expand_batch");
+        std::vector<uint64_t> totals(S);
+        check(hipMemcpy(totals.data(), total_.get(), 8 * S, hipMemcpyDeviceToHost),
+              "totals D2H");
+        uint64_t launched = S * pl.n_att;
+        for (uint64_t s = 0; s < S; ++s) {
+            if (totals[s] >= len) continue;
+            launched += finish(key_.get() + 8 * s, start_words[s], out_lo + s * seed_stride,
+                               out_hi ? out_hi + s * seed_stride : nullptr, len, order,
+                               prng_nbytes, totals[s], pl.n_att, 0) -
+                        pl.n_att;
+        }
+        return launched;
+    }
+
+  private:
+    // The single-seed loop, from `filled` elements in place after `attempt`
+    // attempts of the stream (0, 0 for a fresh seed): launch, read back the
+    // accepted count, repeat until `len` are filled. first_attempts != 0
+    // sizes the first launch. Returns the attempts launched, `attempt`
+    // included.
+    uint64_t finish(const uint32_t* key_dev, uint64_t start_word, uint64_t* out_lo,
+                    uint64_t* out_hi, uint64_t len, const Limbs& order, int prng_nbytes,
+                    uint64_t filled, uint64_t attempt, uint64_t first_attempts) {
+        const int L = order.n;
+        total_.reserve(1, "alloc total");
         while (filled < len) {
-            uint64_t remaining = len - filled;
-            double exp_att = double(remaining) / p;
-            uint64_t n_att = uint64_t(exp_att + 6.0 * std::sqrt(exp_att / p) + 1024.0);
-            // multi-limb orders accept as few as 1 draw in 200: cap the launch
-            // so the workspace does not grow with 1/p, and loop
-            if (L > 2 && n_att > kMaxAttemptsPerLaunch) n_att = kMaxAttemptsPerLaunch;
+            const Plan pl = plan(order, prng_nbytes, len - filled, first_attempts);
+            first_attempts = 0;
+            const uint64_t n_att = pl.n_att;
             // accepted draws compact into per-workgroup segments of `cand`,
             // the last one cut at n_att; counts: one per workgroup
-            uint64_t max_wgs = (n_att + 256 * apt - 1) / (256 * apt) + 2;
+            uint64_t max_wgs = pl.wgs + 2;
             // candidate limb planes: one buffer each for lo and hi, or for
             // multi-limb orders L planes of n_att in the first
             cand_lo_.reserve(L > 2 ? L * n_att : n_att, "alloc cand");
@@ -177,15 +290,15 @@ class MaskExpander {
             scan_tmp_.reserve(max_wgs / 1024 + 2, "alloc scan tmp");
 
             uint32_t n_wgs = 0;
-            check(xhip_k1_candidates_limbs(key_.get(), start_word, attempt, n_att, wpd,
+            check(xhip_k1_candidates_limbs(key_dev, start_word, attempt, n_att, pl.wpd,
                                            prng_nbytes, order.v, cand_lo_.get(), cand_hi,
-                                           counts_.get(), apt, &n_wgs),
+                                           counts_.get(), pl.apt, &n_wgs),
                   "k1_candidates");
             check(xhip_k1_scan_hier(counts_.get(), n_wgs, scan_tmp_.get(), total_.get()),
                   "k1_scan");
             check(xhip_k1_scatter_compact_limbs(cand_lo_.get(), cand_hi, counts_.get(),
-                                                total_.get(), n_wgs, apt, filled, out_lo, out_hi,
-                                                len, order.v),
+                                                total_.get(), n_wgs, pl.apt, filled, out_lo,
+                                                out_hi, len, order.v),
                   "k1_scatter_compact");
             uint64_t round_accepted = 0;
             check(hipMemcpy(&round_accepted, total_.get(), 8, hipMemcpyDeviceToHost),
@@ -193,13 +306,12 @@ class MaskExpander {
             filled += round_accepted;  // may overshoot len; clamped below
             if (filled > len) filled = len;
             attempt += n_att;
-            if (round_accepted == 0 && n_att > 0 && p <= 0.0)
+            if (round_accepted == 0 && n_att > 0 && pl.p <= 0.0)
                 throw std::runtime_error("expand: zero acceptance");
         }
         return attempt;
     }
 
-  private:
     // 2^22 attempts: 160 MiB of candidate planes at five limbs
     static constexpr uint64_t kMaxAttemptsPerLaunch = uint64_t(1) << 22;
 
@@ -207,8 +319,8 @@ class MaskExpander {
     DeviceBuffer<uint64_t> cand_hi_;  // u128 orders only
     DeviceBuffer<uint32_t> counts_;   // accepted per candidates workgroup
     DeviceBuffer<uint32_t> scan_tmp_;
-    DeviceBuffer<uint64_t> total_;
-    DeviceBuffer<uint32_t> key_;
+    DeviceBuffer<uint64_t> total_;    // accepted per seed of the launch
+    DeviceBuffer<uint32_t> key_;      // S keys (8 words each), then S u64 start words
 };
 
 PYBIND11_MODULE(_hip, m) {
@@ -239,9 +351,27 @@ PYBIND11_MODULE(_hip, m) {
     // 10^45 for f32 Bmax).
     py::class_<MaskExpander>(m, "MaskExpander")
         .def(py::init<>())
-        .def("expand", &MaskExpander::expand, py::arg("seed"), py::arg("out_lo"),
-             py::arg("out_hi"), py::arg("len"), py::arg("order"), py::arg("prng_nbytes"),
-             py::arg("start_word"), nogil);
+        // seed: 32*S bytes; start_word: an int, or S of them
+        .def(
+            "expand",
+            [](MaskExpander& self, const std::string& seed, uintptr_t out_lo, uintptr_t out_hi,
+               uint64_t len, const std::string& order, int prng_nbytes, py::object start_word,
+               uint64_t seed_stride, uint64_t attempts) {
+                std::vector<uint64_t> words;
+                if (py::isinstance<py::int_>(start_word))
+                    words.push_back(start_word.cast<uint64_t>());
+                else
+                    words = start_word.cast<std::vector<uint64_t>>();
+                py::gil_scoped_release release;
+                return self.expand(seed, out_lo, out_hi, len, order, prng_nbytes, words,
+                                   seed_stride, attempts);
+            },
+            py::arg("seed"), py::arg("out_lo"), py::arg("out_hi"), py::arg("len"),
+            py::arg("order"), py::arg("prng_nbytes"), py::arg("start_word"), py::kw_only(),
+            py::arg("seed_stride") = 0, py::arg("attempts") = 0)
+        // private: the engine's batch size (the batch rule lives in plan())
+        .def_static("_batch_size", &MaskExpander::batch_size, py::arg("len"), py::arg("order"),
+                    py::arg("prng_nbytes"), py::arg("budget_bytes"));
 
     m.def(
         "aggregate_batch",
@@ -322,19 +452,26 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("planes"), py::arg("out_lo"), py::arg("out_hi"), py::arg("len"),
         py::arg("n_planes"), py::arg("order"), py::arg("digit_bits") = 32, nogil);
 
-    // canonical values -> add into [n_planes][len] planes of digit_bits-wide digits
+    // canonical values -> add into [n_planes][len] planes of digit_bits-wide
+    // digits; `rows` value vectors, row_stride u64 elements apart, in one call
     m.def(
         "add_to_planes",
         [](uintptr_t planes, uintptr_t lo, uintptr_t hi, uint64_t len, int n_planes,
-           const std::string& order, int digit_bits) {
+           const std::string& order, int digit_bits, uint32_t rows, uint64_t row_stride) {
             Limbs o = parse_order(order, hi);
             check_digit_bits(o, digit_bits);
-            check(xhip_add_to_planes_limbs(u64p(planes), u64p(lo), u64p(hi), len, n_planes,
-                                           digit_bits, o.v),
+            if (rows < 1 || rows > XHIP_K1_MAX_BATCH)
+                throw py::value_error("rows must be in 1..65535");
+            if (rows > 1 && (row_stride == 0 || row_stride < len))
+                throw py::value_error("several rows need row_stride, the u64 elements between "
+                                      "them (at least len)");
+            check(xhip_add_rows_to_planes_limbs(u64p(planes), u64p(lo), u64p(hi), len, n_planes,
+                                                digit_bits, o.v, rows, row_stride),
                   "add_to_planes");
         },
         py::arg("planes"), py::arg("lo"), py::arg("hi"), py::arg("len"), py::arg("n_planes"),
-        py::arg("order"), py::arg("digit_bits") = 32, nogil);
+        py::arg("order"), py::arg("digit_bits") = 32, py::kw_only(), py::arg("rows") = 1,
+        py::arg("row_stride") = 0, nogil);
 
     // wide orders only: 32-bit accumulator planes -> k compact planes of the
     // value mod order

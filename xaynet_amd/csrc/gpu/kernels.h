@@ -34,6 +34,13 @@ hipError_t xhip_k1_candidates(const uint32_t* key8_dev, uint64_t start_word,
                               int nbytes, uint64_t order_lo, uint64_t order_hi,
                               uint64_t* cand_lo, uint64_t* cand_hi, uint32_t* wg_counts,
                               int attempts_per_thread, uint32_t* n_wgs_out);
+// Up to this many counts xhip_k1_scan_hier runs one workgroup. It is also the
+// batch rule: seeds are expanded together (xhip_k1_expand_batch, one scan
+// workgroup per seed) only while one seed's launch has at most this many
+// candidate workgroups.
+#define XHIP_K1_SCAN_ONE_WG 2048
+// seeds per batched launch (the grid's second dimension), rows per row sum
+#define XHIP_K1_MAX_BATCH 65535
 // blk_tmp must hold ceil(n/1024) u32
 hipError_t xhip_k1_scan_hier(uint32_t* wg_counts, uint32_t n, uint32_t* blk_tmp,
                              uint64_t* total_dev);
@@ -41,6 +48,19 @@ hipError_t xhip_k1_scatter_compact(const uint64_t* cand_lo, const uint64_t* cand
                                    const uint32_t* wg_offsets, const uint64_t* total_dev,
                                    uint32_t n_wgs, int apt, uint64_t out_base, uint64_t* out_lo,
                                    uint64_t* out_hi, uint64_t out_len);
+// Batched expansion for u64 and u128 orders: seed s (key keys_dev + 8*s, unit
+// draw of start_words_dev[s] keystream words) gets n_attempts attempts from
+// attempt 0, candidate segments at cand + s*cand_stride (>= wgs*256*apt), row
+// s of wg_counts (counts_stride >= wgs), its accepted count in totals_dev[s]
+// and its values in out_lo/out_hi + s*out_stride, cut at out_len.
+// wgs = ceil(n_attempts / (256*apt)) must not exceed XHIP_K1_SCAN_ONE_WG.
+hipError_t xhip_k1_expand_batch(const uint32_t* keys_dev, const uint64_t* start_words_dev,
+                                uint32_t n_seeds, uint64_t n_attempts, int words_per_draw,
+                                int nbytes, uint64_t order_lo, uint64_t order_hi,
+                                uint64_t* cand_lo, uint64_t* cand_hi, uint64_t cand_stride,
+                                uint32_t* wg_counts, uint32_t counts_stride,
+                                uint64_t* totals_dev, int apt, uint64_t* out_lo,
+                                uint64_t* out_hi, uint64_t out_stride, uint64_t out_len);
 
 // ---- K3: batched aggregation (ept <= 0 picks the per-bpn default) ----
 hipError_t xhip_k3_aggregate(uint64_t* acc, const uint8_t* updates, uint64_t stride,
@@ -119,6 +139,10 @@ hipError_t xhip_k2_canonicalize_limbs(const uint64_t* planes, uint64_t* out_lo,
 hipError_t xhip_add_to_planes_limbs(uint64_t* planes, const uint64_t* lo, const uint64_t* hi,
                                     uint64_t len, int n_planes, int digit_bits,
                                     xhip_limbs order);
+hipError_t xhip_add_rows_to_planes_limbs(uint64_t* planes, const uint64_t* lo,
+                                         const uint64_t* hi, uint64_t len, int n_planes,
+                                         int digit_bits, xhip_limbs order, uint32_t rows,
+                                         uint64_t row_stride);
 hipError_t xhip_k2_recode_planes_limbs(const uint64_t* acc, uint64_t* out, uint64_t len,
                                        int n_digits, xhip_limbs order, int k, int digit_bits);
 hipError_t xhip_k2_mod_add_limbs(uint64_t* a_lo, uint64_t* a_hi, const uint64_t* b_lo,

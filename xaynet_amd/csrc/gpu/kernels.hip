@@ -117,98 +117,32 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t mine, uint32_t* wav
 // word i lives at lds[i*257 + b]. Writes (lane = block) and window reads
 // (lane-consecutive blocks, same word index) are then bank-conflict-free —
 // the natural block-major layout had a 47% conflict rate (PMC, r2).
+//
+// The kernel body is k1_candidates_lds_body.inc, shared with the batched
+// kernel below (one seed per grid row).
 extern "C" __global__ void __launch_bounds__(K1_LDS_THREADS) k1_candidates_lds(
     const uint32_t* __restrict__ key8, uint64_t start_word, uint64_t first_attempt,
     uint64_t n_attempts, int words_per_draw, int nbytes, uint64_t order,
     uint64_t* __restrict__ cand, uint32_t* __restrict__ wg_counts, int draws_per_thread) {
-    __shared__ uint32_t lds_words[16 * 257];
-    __shared__ uint32_t wave_tot[4];
+#include "k1_candidates_lds_body.inc"
+}
 
-    uint32_t key[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) key[i] = key8[i];
-
-    // keystream words covered by this workgroup: [W0, W0 + 256*16)
-    // (each thread's draws_per_thread * words_per_draw == 16 words)
-    uint64_t W0 = start_word + first_attempt * uint64_t(words_per_draw) +
-                  uint64_t(blockIdx.x) * K1_LDS_THREADS * 16;
-    uint64_t first_blk = W0 >> 4;
-    int off0 = int(W0 & 15);
-
-    uint32_t tmp[16];
-    chacha20_block_dev(key, first_blk + threadIdx.x, tmp);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) lds_words[i * 257 + threadIdx.x] = tmp[i];
-    if (off0 && threadIdx.x == 0) {  // boundary straddle block
-        chacha20_block_dev(key, first_blk + K1_LDS_THREADS, tmp);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) lds_words[i * 257 + K1_LDS_THREADS] = tmp[i];
-    }
-    __syncthreads();
-
-    // Accepted draws are compacted IN ORDER into this workgroup's segment of
-    // `cand` (base = wg * 256 * dpt, its worst-case capacity), so the
-    // scatter pass is a coalesced segment copy.
-    uint64_t t = uint64_t(blockIdx.x) * K1_LDS_THREADS + threadIdx.x;
-    uint64_t a0 = t * draws_per_thread;
-    // Accepted draws are recorded as a BITMASK and re-extracted from LDS in
-    // a second pass after the scan: value arrays indexed by a dynamic
-    // count (`vals[mine++]`) compile to per-element select chains, which
-    // cost more than re-reading the LDS window.
-    int wbase = off0 + (int(threadIdx.x) << 4);  // this thread's first word
-    auto ldw = [&](int w) { return lds_words[(w & 15) * 257 + (w >> 4)]; };
-    auto extract = [&](int d) {
-        int w = wbase + d * words_per_draw;
-        uint64_t v = uint64_t(ldw(w));
-        if (nbytes > 4) {
-            uint64_t hi = uint64_t(ldw(w + 1));
-            int hb = nbytes - 4;
-            hi &= (hb >= 4) ? 0xffffffffULL : ((1ULL << (8 * hb)) - 1);
-            v |= hi << 32;
-        } else if (nbytes < 4) {
-            v &= (1ULL << (8 * nbytes)) - 1;
-        }
-        return v;
-    };
-    uint32_t accept_bits = 0;
-    uint32_t mine = 0;
-    if (a0 < n_attempts) {
-#pragma unroll 4
-        for (int d = 0; d < draws_per_thread; ++d) {
-            if (a0 + d >= n_attempts) break;
-            if (extract(d) < order) {
-                accept_bits |= 1u << d;
-                ++mine;
-            }
-        }
-    }
-    // block_excl_scan<4>, written out: calling the helper here changes this
-    // kernel's register allocation (41 -> 40 SGPRs, acceptance loop
-    // rescheduled), and K1's hottest kernel keeps its measured code
-    uint32_t lane = threadIdx.x & 63;
-    uint32_t wave = threadIdx.x >> 6;
-    uint32_t incl = mine;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        uint32_t v = __shfl_up(incl, off, 64);
-        if (int(lane) >= off) incl += v;
-    }
-    if (lane == 63) wave_tot[wave] = incl;
-    __syncthreads();
-    uint32_t wave_base = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < 4; ++w) {
-        if (w < wave) wave_base += wave_tot[w];
-    }
-    uint32_t excl = wave_base + incl - mine;
-    uint64_t k = uint64_t(blockIdx.x) * K1_LDS_THREADS * draws_per_thread + excl;
-    while (accept_bits) {
-        int d = __builtin_ctz(accept_bits);
-        accept_bits &= accept_bits - 1;
-        cand[k++] = extract(d);
-    }
-    if (threadIdx.x == K1_LDS_THREADS - 1)
-        wg_counts[blockIdx.x] = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
+// Batched K1a (the sum2 task: many seeds, one launch). Grid row s =
+// blockIdx.y is seed s: its key at keys + 8*s, its own start_words[s] (the
+// unit draw consumes a different number of keystream words per seed, so off0
+// and the straddle block differ per row), its candidate segments at cand_all
+// + s*cand_stride and row s of counts_all. Attempts start at 0.
+extern "C" __global__ void __launch_bounds__(K1_LDS_THREADS) k1_candidates_lds_batch(
+    const uint32_t* __restrict__ keys, const uint64_t* __restrict__ start_words,
+    uint64_t n_attempts, int words_per_draw, int nbytes, uint64_t order,
+    uint64_t* __restrict__ cand_all, uint64_t cand_stride, uint32_t* __restrict__ counts_all,
+    uint32_t counts_stride, int draws_per_thread) {
+    const uint64_t s = blockIdx.y;
+    const uint32_t* key8 = keys + 8 * s;
+    const uint64_t start_word = start_words[s], first_attempt = 0;
+    uint64_t* cand = cand_all + s * cand_stride;
+    uint32_t* wg_counts = counts_all + s * counts_stride;
+#include "k1_candidates_lds_body.inc"
 }
 
 // K1a wide-order variant (orders in (2^64, 2^128], bpn 9..16): every F64
@@ -218,82 +152,33 @@ extern "C" __global__ void __launch_bounds__(K1_LDS_THREADS) k1_candidates_lds(
 // is 16/wpd rounded DOWN (5 for wpd=3), so a workgroup's attempts span at
 // most the 256 staged blocks (+1 boundary). Accepted draws are compacted in
 // order into per-workgroup segments of capacity 256*apt.
+// The kernel body is k1_candidates_lds_u128_body.inc, shared with the batched
+// kernel below.
 extern "C" __global__ void __launch_bounds__(K1_LDS_THREADS) k1_candidates_lds_u128(
     const uint32_t* __restrict__ key8, uint64_t start_word, uint64_t first_attempt,
     uint64_t n_attempts, int words_per_draw, int nbytes,
     uint64_t order_lo, uint64_t order_hi,
     uint64_t* __restrict__ cand_lo, uint64_t* __restrict__ cand_hi,
     uint32_t* __restrict__ wg_counts, int attempts_per_thread) {
-    __shared__ uint32_t lds_words[K1_LDS_THREADS * 16 + 16];
+#include "k1_candidates_lds_u128_body.inc"
+}
 
-    uint32_t key[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) key[i] = key8[i];
-
-    const int apt = attempts_per_thread;  // 5 (wpd=3) or 4 (wpd=4)
-    // words covered by this workgroup's attempts
-    uint64_t A0 = first_attempt + uint64_t(blockIdx.x) * K1_LDS_THREADS * apt;
-    uint64_t W0 = start_word + A0 * uint64_t(words_per_draw);
-    uint64_t first_blk = W0 >> 4;
-    int off0 = int(W0 & 15);
-    // blocks needed: ceil((off0 + 256*apt*wpd) / 16), <= 257
-    int need_blocks = (off0 + K1_LDS_THREADS * apt * words_per_draw + 15) >> 4;
-
-    uint32_t tmp[16];
-    if (int(threadIdx.x) < need_blocks) {
-        chacha20_block_dev(key, first_blk + threadIdx.x, tmp);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) lds_words[(threadIdx.x << 4) + i] = tmp[i];
-    }
-    if (need_blocks > K1_LDS_THREADS && threadIdx.x == 0) {
-        chacha20_block_dev(key, first_blk + K1_LDS_THREADS, tmp);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) lds_words[(K1_LDS_THREADS << 4) + i] = tmp[i];
-    }
-    __syncthreads();
-
-    __shared__ uint32_t wave_tot[4];
-    uint64_t a_rel0 = (uint64_t(blockIdx.x) * K1_LDS_THREADS + threadIdx.x) * apt;
-    // bitmask + re-extract (see k1_candidates_lds): avoids dynamic-indexed
-    // register value arrays
-    int widx = off0 + int(uint64_t(threadIdx.x) * apt) * words_per_draw;
-    auto extract = [&](int d, uint64_t& lo, uint64_t& hi) {
-        const uint32_t* w = &lds_words[widx + d * words_per_draw];
-        lo = uint64_t(w[0]) | (uint64_t(w[1]) << 32);
-        if (nbytes >= 13) {
-            hi = uint64_t(w[2]) | (uint64_t(w[3]) << 32);
-            if (nbytes < 16) hi &= (1ULL << (8 * (nbytes - 8))) - 1;
-        } else {
-            hi = uint64_t(w[2]);
-            if (nbytes < 12) hi &= (1ULL << (8 * (nbytes - 8))) - 1;
-        }
-    };
-    uint32_t accept_bits = 0;
-    uint32_t mine = 0;
-    if (a_rel0 < n_attempts) {
-        for (int d = 0; d < apt; ++d) {
-            if (a_rel0 + d >= n_attempts) break;
-            uint64_t lo, hi;
-            extract(d, lo, hi);
-            if ((hi < order_hi) || (hi == order_hi && lo < order_lo)) {
-                accept_bits |= 1u << d;
-                ++mine;
-            }
-        }
-    }
-    uint64_t k =
-        uint64_t(blockIdx.x) * K1_LDS_THREADS * apt + block_excl_scan<4>(mine, wave_tot);
-    while (accept_bits) {
-        int d = __builtin_ctz(accept_bits);
-        accept_bits &= accept_bits - 1;
-        uint64_t lo, hi;
-        extract(d, lo, hi);
-        cand_lo[k] = lo;
-        cand_hi[k] = hi;
-        ++k;
-    }
-    if (threadIdx.x == K1_LDS_THREADS - 1)
-        wg_counts[blockIdx.x] = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
+// Batched wide K1a: seed s = blockIdx.y, as k1_candidates_lds_batch; both
+// candidate planes share cand_stride.
+extern "C" __global__ void __launch_bounds__(K1_LDS_THREADS) k1_candidates_lds_u128_batch(
+    const uint32_t* __restrict__ keys, const uint64_t* __restrict__ start_words,
+    uint64_t n_attempts, int words_per_draw, int nbytes,
+    uint64_t order_lo, uint64_t order_hi,
+    uint64_t* __restrict__ cand_lo_all, uint64_t* __restrict__ cand_hi_all,
+    uint64_t cand_stride, uint32_t* __restrict__ counts_all, uint32_t counts_stride,
+    int attempts_per_thread) {
+    const uint64_t s = blockIdx.y;
+    const uint32_t* key8 = keys + 8 * s;
+    const uint64_t start_word = start_words[s], first_attempt = 0;
+    uint64_t* cand_lo = cand_lo_all + s * cand_stride;
+    uint64_t* cand_hi = cand_hi_all + s * cand_stride;
+    uint32_t* wg_counts = counts_all + s * counts_stride;
+#include "k1_candidates_lds_u128_body.inc"
 }
 
 extern "C" __global__ void k1_scatter_compact_u128(
@@ -329,6 +214,35 @@ extern "C" __global__ void k1_scatter_compact(
     for (uint64_t i = threadIdx.x; i < end - beg; i += blockDim.x) {
         uint64_t pos = out_base + beg + i;
         if (pos < out_len) out[pos] = src[i];
+    }
+}
+
+// Batched K1c: grid row s = blockIdx.y copies seed s's segments (cand +
+// s*cand_stride, row s of the scanned offsets) into row s of the value
+// matrix: out_lo + s*out_stride, for wide orders ([S, 2, n], out_stride = 2n)
+// out_hi + s*out_stride as well; out_hi is null for u64 orders. The seed's
+// last workgroup ends at totals[s], never at the next seed's first offset;
+// positions at or beyond out_len are dropped.
+template <bool WIDE>
+__global__ void k1_scatter_compact_batch(
+    const uint64_t* __restrict__ cand_lo, const uint64_t* __restrict__ cand_hi,
+    uint64_t cand_stride, const uint32_t* __restrict__ wg_offsets, uint32_t counts_stride,
+    const uint64_t* __restrict__ totals, uint32_t n_wgs, int per_wg_capacity,
+    uint64_t* __restrict__ out_lo, uint64_t* __restrict__ out_hi, uint64_t out_stride,
+    uint64_t out_len) {
+    const uint64_t s = blockIdx.y;
+    const uint32_t wg = blockIdx.x;
+    const uint32_t* offs = wg_offsets + s * counts_stride;
+    uint64_t beg = offs[wg];
+    uint64_t end = (wg + 1 < n_wgs) ? uint64_t(offs[wg + 1]) : totals[s];
+    uint64_t src = s * cand_stride + uint64_t(wg) * per_wg_capacity;
+    uint64_t dst = s * out_stride;
+    for (uint64_t i = threadIdx.x; i < end - beg; i += blockDim.x) {
+        uint64_t pos = beg + i;
+        if (pos < out_len) {
+            out_lo[dst + pos] = cand_lo[src + i];
+            if constexpr (WIDE) out_hi[dst + pos] = cand_hi[src + i];
+        }
     }
 }
 
@@ -393,8 +307,8 @@ extern "C" __global__ void __launch_bounds__(256) k1_scan_addbase(
 // slice writing prefixes. The previous chunked Hillis-Steele version
 // needed ~22 barriers per 1024 counts (99-169 us per mask expansion at
 // 25M — as large as the scatter pass); this one needs two.
-extern "C" __global__ void k1_scan(uint32_t* __restrict__ wg_counts, uint32_t n,
-                                   uint64_t* __restrict__ total) {
+__device__ __forceinline__ void k1_scan_body(uint32_t* __restrict__ wg_counts, uint32_t n,
+                                             uint64_t* __restrict__ total) {
     __shared__ uint32_t wave_sums[16];
     uint32_t T = blockDim.x;  // 1024
     uint32_t seg = (n + T - 1) / T;
@@ -411,6 +325,18 @@ extern "C" __global__ void k1_scan(uint32_t* __restrict__ wg_counts, uint32_t n,
     }
     // the last thread's running prefix has passed every count
     if (threadIdx.x == T - 1) *total = run;
+}
+
+extern "C" __global__ void k1_scan(uint32_t* __restrict__ wg_counts, uint32_t n,
+                                   uint64_t* __restrict__ total) {
+    k1_scan_body(wg_counts, n, total);
+}
+
+// Segmented scan for the batched path: workgroup s scans seed s's row of n
+// counts (n <= 2048, the single-workgroup range) and writes totals[s].
+extern "C" __global__ void k1_scan_seg(uint32_t* __restrict__ wg_counts, uint32_t counts_stride,
+                                       uint32_t n, uint64_t* __restrict__ totals) {
+    k1_scan_body(wg_counts + uint64_t(blockIdx.x) * counts_stride, n, totals + blockIdx.x);
 }
 
 // ------------------------------------------------- K3: batched aggregation
@@ -699,6 +625,29 @@ extern "C" __global__ void k_add_u64_to_planes(
     for (int d = 0; d < n_digits; ++d) acc[uint64_t(d) * len + i] += (v >> (32 * d)) & 0xffffffffULL;
 }
 
+// Row sum into planes (the batched sum2 task): `rows` value vectors, row r at
+// vals + r*row_stride, are summed digit by digit in registers and added into
+// the planes ONCE — one read of every row plus one plane pass, where `rows`
+// calls of the kernel above (or of k2_mod_add) re-read and re-write the
+// running total every time. Digits are below 2^32 and rows at most 65535, so
+// the register sums stay below 2^48. n_digits is 1 or 2.
+extern "C" __global__ void k_add_rows_u64_to_planes(
+    uint64_t* __restrict__ acc, const uint64_t* __restrict__ vals, uint64_t row_stride,
+    uint32_t rows, uint64_t len, int n_digits) {
+    uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= len) return;
+    const uint64_t* p = vals + i;
+    uint64_t d0 = 0, d1 = 0;
+#pragma unroll 4
+    for (uint32_t r = 0; r < rows; ++r) {
+        uint64_t v = p[uint64_t(r) * row_stride];
+        d0 += v & 0xffffffffULL;
+        d1 += v >> 32;
+    }
+    acc[i] += d0;
+    if (n_digits > 1) acc[len + i] += d1;
+}
+
 // ------------------------------------------------- u128-order variants
 //
 // Group orders in (2^64, 2^128] (bpn 9..16): every F64 non-Bmax config and
@@ -812,6 +761,32 @@ extern "C" __global__ void k_add_u128_to_planes(
     if (i >= len) return;
     unsigned __int128 v = ((unsigned __int128)hi[i] << 64) | lo[i];
     for (int j = 0; j < k; ++j) planes[uint64_t(j) * len + i] += u128_digit(v, j, digit_bits);
+}
+
+// Wide row sum into 32-bit planes (see k_add_rows_u64_to_planes): row r's
+// split values at lo + r*row_stride and hi + r*row_stride ([S, 2, n]:
+// row_stride = 2n), k <= 4 planes.
+extern "C" __global__ void k_add_rows_u128_to_planes(
+    uint64_t* __restrict__ planes, const uint64_t* __restrict__ lo,
+    const uint64_t* __restrict__ hi, uint64_t row_stride, uint32_t rows, uint64_t len, int k) {
+    uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= len) return;
+    const uint64_t* pl = lo + i;
+    const uint64_t* ph = hi + i;
+    uint64_t d0 = 0, d1 = 0, d2 = 0, d3 = 0;
+#pragma unroll 2
+    for (uint32_t r = 0; r < rows; ++r) {
+        uint64_t l = pl[uint64_t(r) * row_stride];
+        uint64_t h = ph[uint64_t(r) * row_stride];
+        d0 += l & 0xffffffffULL;
+        d1 += l >> 32;
+        d2 += h & 0xffffffffULL;
+        d3 += h >> 32;
+    }
+    planes[i] += d0;
+    if (k > 1) planes[len + i] += d1;
+    if (k > 2) planes[2 * len + i] += d2;
+    if (k > 3) planes[3 * len + i] += d3;
 }
 
 // Fused re-digitisation for the cross-rank reduce-scatter: 32-bit accumulator
@@ -1347,7 +1322,7 @@ hipError_t xhip_k1_candidates(const uint32_t* key8_dev, uint64_t start_word,
 // tiny middle scan over the tile totals + base add.
 hipError_t xhip_k1_scan_hier(uint32_t* wg_counts, uint32_t n, uint32_t* blk_tmp,
                              uint64_t* total_dev) {
-    if (n <= 2048) {
+    if (n <= XHIP_K1_SCAN_ONE_WG) {
         hipLaunchKernelGGL(k1_scan, dim3(1), dim3(1024), 0, 0, wg_counts, n, total_dev);
         return hipGetLastError();
     }
@@ -1370,6 +1345,44 @@ hipError_t xhip_k1_scatter_compact(const uint64_t* cand_lo, const uint64_t* cand
     else
         hipLaunchKernelGGL(k1_scatter_compact, dim3(n_wgs), dim3(256), 0, 0, cand_lo,
                            wg_offsets, total_dev, n_wgs, 256 * apt, out_base, out_lo, out_len);
+    return hipGetLastError();
+}
+
+// Batched K1 for L <= 2: every seed's candidates, segmented scan and scatter
+// in three launches, grid row s = seed s.
+hipError_t xhip_k1_expand_batch(const uint32_t* keys_dev, const uint64_t* start_words_dev,
+                                uint32_t n_seeds, uint64_t n_attempts, int words_per_draw,
+                                int nbytes, uint64_t order_lo, uint64_t order_hi,
+                                uint64_t* cand_lo, uint64_t* cand_hi, uint64_t cand_stride,
+                                uint32_t* wg_counts, uint32_t counts_stride,
+                                uint64_t* totals_dev, int apt, uint64_t* out_lo,
+                                uint64_t* out_hi, uint64_t out_stride, uint64_t out_len) {
+    if (apt < 1 || n_attempts == 0) return hipErrorInvalidValue;
+    const uint64_t cap = uint64_t(K1_LDS_THREADS) * apt;
+    const uint64_t wgs64 = (n_attempts + cap - 1) / cap;
+    // the segmented scan is the single-workgroup scan, one row per seed
+    if (n_seeds < 1 || n_seeds > XHIP_K1_MAX_BATCH || wgs64 > XHIP_K1_SCAN_ONE_WG ||
+        counts_stride < wgs64 || cand_stride < wgs64 * cap ||
+        (order_hi != 0) != (out_hi != nullptr) || (order_hi != 0 && !cand_hi))
+        return hipErrorInvalidValue;
+    const uint32_t wgs = uint32_t(wgs64);
+    const dim3 grid(wgs, n_seeds);
+    if (order_hi != 0)
+        hipLaunchKernelGGL(k1_candidates_lds_u128_batch, grid, dim3(K1_LDS_THREADS), 0, 0,
+                           keys_dev, start_words_dev, n_attempts, words_per_draw, nbytes,
+                           order_lo, order_hi, cand_lo, cand_hi, cand_stride, wg_counts,
+                           counts_stride, apt);
+    else
+        hipLaunchKernelGGL(k1_candidates_lds_batch, grid, dim3(K1_LDS_THREADS), 0, 0, keys_dev,
+                           start_words_dev, n_attempts, words_per_draw, nbytes, order_lo,
+                           cand_lo, cand_stride, wg_counts, counts_stride, apt);
+    hipLaunchKernelGGL(k1_scan_seg, dim3(n_seeds), dim3(1024), 0, 0, wg_counts, counts_stride,
+                       wgs, totals_dev);
+    hipLaunchKernelGGL(order_hi != 0 ? k1_scatter_compact_batch<true>
+                                     : k1_scatter_compact_batch<false>,
+                       grid, dim3(256), 0, 0, cand_lo, cand_hi, cand_stride, wg_counts,
+                       counts_stride, totals_dev, wgs, int(cap), out_lo, out_hi, out_stride,
+                       out_len);
     return hipGetLastError();
 }
 
@@ -1714,6 +1727,32 @@ hipError_t xhip_add_to_planes_limbs(uint64_t* planes, const uint64_t* lo, const 
         return launch_1d(k_add_ml_to_planes<decltype(l)::value>, len, planes, lo,
                          row_stride(lo, hi), len, n_planes, digit_bits);
     });
+}
+
+// `rows` value vectors, row r at lo/hi + r*row_stride, into the planes: one
+// launch for L <= 2 into 32-bit planes, else the one-row kernel per row.
+hipError_t xhip_add_rows_to_planes_limbs(uint64_t* planes, const uint64_t* lo,
+                                         const uint64_t* hi, uint64_t len, int n_planes,
+                                         int digit_bits, xhip_limbs order, uint32_t rows,
+                                         uint64_t row_stride) {
+    const int n = n_limbs_of(order);
+    if (rows < 1 || rows > XHIP_K1_MAX_BATCH) return hipErrorInvalidValue;
+    if (rows == 1)
+        return xhip_add_to_planes_limbs(planes, lo, hi, len, n_planes, digit_bits, order);
+    if (n <= 2 && digit_bits == 32 && n_planes >= 1 && n_planes <= (hi ? 4 : 2)) {
+        if (!hi)
+            return launch_1d(k_add_rows_u64_to_planes, len, planes, lo, row_stride, rows, len,
+                             n_planes);
+        return launch_1d(k_add_rows_u128_to_planes, len, planes, lo, hi, row_stride, rows, len,
+                         n_planes);
+    }
+    for (uint32_t r = 0; r < rows; ++r) {
+        hipError_t e = xhip_add_to_planes_limbs(planes, lo + r * row_stride,
+                                                hi ? hi + r * row_stride : nullptr, len,
+                                                n_planes, digit_bits, order);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 hipError_t xhip_k2_recode_planes_limbs(const uint64_t* acc, uint64_t* out, uint64_t len,

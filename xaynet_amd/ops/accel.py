@@ -11,7 +11,8 @@ lazily build (and cache) one engine per (config, length). They fall back to
 the CPU path (return None) on any error, so a GPU-less box or an
 out-of-range config degrades cleanly. Replaces: Masker::mask
 (masking.rs:358-404) via K1+K5w and the sum2 derive+aggregate loop
-(xaynet-sdk sum2.rs:170-190) via K1+K2."""
+(xaynet-sdk sum2.rs:170-190) via batched K1 and a row sum into digit planes
+(ops/sum2.py)."""
 from __future__ import annotations
 
 import logging

@@ -38,13 +38,20 @@ def _cfg_scalars(cfg):
     }
 
 
+# Workspace budget of the batched sum2 path (value rows + candidate planes of
+# one batch), from the sweep in profiles/r07_sum2_batch.md.
+DEFAULT_SUM2_BUDGET_BYTES = 1 << 30
+MAX_SUM2_ROWS = 65535  # rows one row-sum launch takes
+
+
 class MaskedAggregatorBase:
     """Digit-plane aggregation state of one model: int64 [n_digits, length]
     accumulator planes plus the exact masked scalar sum."""
 
     _TORCH_DTYPES = {0: torch.float32, 1: torch.float64, 2: torch.int32, 3: torch.int64}
 
-    def __init__(self, vect_cfg, unit_cfg, length: int, device):
+    def __init__(self, vect_cfg, unit_cfg, length: int, device,
+                 sum2_budget_bytes: int = DEFAULT_SUM2_BUDGET_BYTES):
         if vect_cfg.bytes_per_number > MAX_BYTES_PER_NUMBER:
             raise ValueError(
                 f"{type(self).__name__} covers group orders up to 2^320 (got "
@@ -67,6 +74,11 @@ class MaskedAggregatorBase:
         self.acc = torch.zeros(self.n_digits, length, dtype=torch.int64, device=self.device)
         self.nb_models = 0
         self.unit_acc = 0  # masked scalar sum (CPU, exact)
+        # sum2 task (ops/sum2.py): planes and value rows of its own, made on
+        # first use; self.acc belongs to update aggregation
+        self.sum2_budget_bytes = int(sum2_budget_bytes)
+        self._sum2_planes = None
+        self._sum2_rows = None
 
     def reset(self):
         self.acc.zero_()
@@ -81,6 +93,34 @@ class MaskedAggregatorBase:
         shape = (self.n_limbs, n) if self.wide else (n,)
         make = torch.zeros if zero else torch.empty
         return make(*shape, dtype=torch.int64, device=self.device)
+
+    def new_rows(self, s: int) -> torch.Tensor:
+        """s canonical value tensors in one: int64 [s, n], or [s, n_limbs, n]
+        when the order is wide (what derive_mask_values_batch fills)."""
+        shape = (s, self.n_limbs, self.length) if self.wide else (s, self.length)
+        return torch.empty(*shape, dtype=torch.int64, device=self.device)
+
+    # ---------------- sum2 workspace ----------------
+
+    @property
+    def sum2_group(self) -> int:
+        """Masks summed by one add_rows_to_planes pass of the sum2 task: the
+        value rows get half the workspace budget (the other half is for the
+        candidate planes of a batch, which are at least as large)."""
+        row_bytes = 8 * self.n_limbs * max(self.length, 1)
+        return max(1, min(MAX_SUM2_ROWS, self.sum2_budget_bytes // (2 * row_bytes)))
+
+    def sum2_workspace(self, n_seeds: int):
+        """(zeroed planes, value rows) of the sum2 task: [n_digits, length]
+        and min(n_seeds, sum2_group) rows, kept between calls."""
+        if self._sum2_planes is None:
+            self._sum2_planes = torch.empty_like(self.acc)
+        rows = min(n_seeds, self.sum2_group)
+        if self._sum2_rows is None or self._sum2_rows.shape[0] < rows:
+            self._sum2_rows = None  # free before growing
+            self._sum2_rows = self.new_rows(rows)
+        self._sum2_planes.zero_()
+        return self._sum2_planes, self._sum2_rows
 
     # ---------------- update staging ----------------
 

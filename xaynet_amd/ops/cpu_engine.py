@@ -27,7 +27,7 @@ import torch
 
 from xaynet_amd import _core
 
-from .base import MaskedAggregatorBase
+from .base import DEFAULT_SUM2_BUDGET_BYTES, MaskedAggregatorBase
 
 _U64 = np.uint64
 _M64 = (1 << 64) - 1
@@ -47,8 +47,9 @@ class CpuPlaneAggregator(MaskedAggregatorBase):
 
     _NP_DTYPES = {0: np.float32, 1: np.float64, 2: np.int32, 3: np.int64}
 
-    def __init__(self, vect_cfg, unit_cfg, length: int, device: str = "cpu"):
-        super().__init__(vect_cfg, unit_cfg, length, "cpu")
+    def __init__(self, vect_cfg, unit_cfg, length: int, device: str = "cpu",
+                 sum2_budget_bytes: int = DEFAULT_SUM2_BUDGET_BYTES):
+        super().__init__(vect_cfg, unit_cfg, length, "cpu", sum2_budget_bytes)
 
     # ---------------- value tensors <-> python ints ----------------
 
@@ -119,6 +120,25 @@ class CpuPlaneAggregator(MaskedAggregatorBase):
         obj = _core.mask.derive_mask(seed, self.length, pair)
         limbs = np.frombuffer(obj.vect_bytes, dtype=np.uint8).reshape(self.length, self.bpn)
         return self._ret(self._limbs_to_tensor(limbs), out)
+
+    @property
+    def batch_size(self) -> int:
+        """There is no launch to share here: the rows of one sum pass, and 1
+        for multi-limb orders as on the GPU."""
+        return 1 if self.n_limbs > 2 else self.sum2_group
+
+    def derive_mask_values_batch(self, seeds, out: torch.Tensor | None = None) -> torch.Tensor:
+        seeds = [bytes(s) for s in seeds]
+        out = self.new_rows(len(seeds)) if out is None else out
+        if out.shape[0] != len(seeds):
+            raise ValueError("derive_mask_values_batch: one row per seed")
+        for s, seed in enumerate(seeds):
+            self.derive_mask_values(seed, out=out[s])
+        return out
+
+    def add_rows_to_planes(self, rows: torch.Tensor, planes: torch.Tensor):
+        for row in rows:
+            self.values_to_planes(row, planes)
 
     # ---------------- aggregation ----------------
 
@@ -253,3 +273,13 @@ class CpuPlaneAggregator(MaskedAggregatorBase):
                       digit_bits: int = 32) -> torch.Tensor:
         return self._finalize(self._planes_to_ints(planes, digit_bits), mask_values, mask_unit,
                               nb_models, dtype)
+
+    # ---------------- wire format ----------------
+
+    def wire_object(self, limbs: torch.Tensor, unit_value: int) -> bytes:
+        """MaskObject wire bytes (MaskVect || MaskUnit) from packed limbs and
+        the unit value."""
+        ubpn = self.unit_cfg.bytes_per_number
+        return (bytes(self.vect_cfg.to_bytes()) + (limbs.numel() // self.bpn).to_bytes(4, "big")
+                + limbs.numpy().tobytes() + bytes(self.unit_cfg.to_bytes())
+                + int(unit_value).to_bytes(ubpn, "little"))

@@ -29,7 +29,7 @@ import torch
 
 from xaynet_amd import _core
 
-from .base import MaskedAggregatorBase, _cfg_scalars
+from .base import DEFAULT_SUM2_BUDGET_BYTES, MaskedAggregatorBase, _cfg_scalars
 
 try:
     from xaynet_amd import _hip
@@ -54,9 +54,10 @@ class GpuMaskedAggregator(MaskedAggregatorBase):
 
     _WEIGHT_DTYPES = {torch.float32: 0, torch.float64: 1, torch.int32: 2, torch.int64: 3}
 
-    def __init__(self, vect_cfg, unit_cfg, length: int, device: str = "cuda"):
+    def __init__(self, vect_cfg, unit_cfg, length: int, device: str = "cuda",
+                 sum2_budget_bytes: int = DEFAULT_SUM2_BUDGET_BYTES):
         _require_gpu()
-        super().__init__(vect_cfg, unit_cfg, length, device)
+        super().__init__(vect_cfg, unit_cfg, length, device, sum2_budget_bytes)
         with torch.cuda.device(self.device):
             self._expander = _hip.MaskExpander()
         self._wire_pin = None  # cached pinned staging buffer of wire_object
@@ -99,6 +100,50 @@ class GpuMaskedAggregator(MaskedAggregatorBase):
         _, unit_words = _core.mask.unit_draw(seed, self.unit_cfg)
         self._expander.expand(seed, lo, hi, n, self.order, self.prng_nbytes, unit_words)
         return out
+
+    @property
+    def batch_size(self) -> int:
+        """Seeds derive_mask_values_batch expands per launch: as many as keep
+        their value rows and candidate planes within sum2_budget_bytes; 1 for
+        multi-limb orders and where one seed's launch is past the
+        single-workgroup scan (the rule is MaskExpander's)."""
+        return _hip.MaskExpander._batch_size(self.length, self.order, self.prng_nbytes,
+                                             self.sum2_budget_bytes)
+
+    def _rows(self, rows: torch.Tensor):
+        """[S, n] / [S, n_limbs, n] value rows -> (lo_ptr, hi_ptr, n, S,
+        row stride in elements)."""
+        if rows.dim() != 2 + self.wide or not rows.is_contiguous() or rows.shape[0] < 1:
+            raise ValueError("value rows must be a contiguous [S, "
+                             + (f"{self.n_limbs}, " if self.wide else "") + "n] int64 tensor")
+        lo, hi, n = self._vals(rows[0])
+        return lo, hi, n, rows.shape[0], rows.stride(0)
+
+    def derive_mask_values_batch(self, seeds, out: torch.Tensor | None = None) -> torch.Tensor:
+        """Expand every seed: row s of the result is derive_mask_values(seeds[s]),
+        bit for bit. batch_size seeds share one candidates -> scan -> scatter
+        pass, one copy of keys in and one of accepted counts out."""
+        seeds = [bytes(s) for s in seeds]
+        out = self.new_rows(len(seeds)) if out is None else out
+        lo, hi, n, rows, stride = self._rows(out)
+        if rows != len(seeds):
+            raise ValueError("derive_mask_values_batch: one row per seed")
+        words = [_core.mask.unit_draw(s, self.unit_cfg)[1] for s in seeds]
+        step = self.batch_size
+        for i in range(0, rows, step):
+            off = 8 * i * stride
+            self._expander.expand(b"".join(seeds[i:i + step]), lo + off, hi + off if hi else 0,
+                                  n, self.order, self.prng_nbytes, words[i:i + step],
+                                  seed_stride=stride)
+        return out
+
+    def add_rows_to_planes(self, rows: torch.Tensor, planes: torch.Tensor):
+        """Add every row of an [S, n] / [S, n_limbs, n] value tensor into a
+        contiguous [k, n] tensor of 32-bit digit planes: the rows' digits are
+        summed in registers and the planes touched once."""
+        lo, hi, n, s, stride = self._rows(rows)
+        ptr, k = self._planes(planes, n)
+        _hip.add_to_planes(ptr, lo, hi, n, k, self.order, 32, rows=s, row_stride=stride)
 
     # ---------------- aggregation (K3) ----------------
 
