@@ -143,6 +143,120 @@ def test_k3_wide_variants_agree():
         assert (planes[ept] == planes[2]).all(), f"wide variant ept={ept} diverges"
 
 
+# ---------------------------------------------- K3: every instantiation
+#
+# bytes per number -> (default, alternate, alternate) elements per thread, the
+# K3_CASE lines of xhip_k3_aggregate; bpn <= 8 also has the LDS-staged kernels
+# (ept 201 / 202: 2048- / 4096-element tiles).
+K3_EPTS = {
+    1: (16, 32, 16), 2: (8, 16, 8), 3: (16, 16, 16), 4: (4, 8, 16), 5: (16, 16, 16),
+    6: (8, 8, 8), 7: (4, 8, 16), 8: (4, 2, 8), 9: (4, 4, 4), 10: (2, 4, 8), 11: (4, 4, 4),
+    12: (2, 4, 2), 13: (4, 4, 4), 14: (2, 4, 2), 15: (4, 4, 4), 16: (2, 4, 1),
+    18: (2, 2, 2), 37: (4, 4, 4), 38: (2, 2, 2), 39: (4, 4, 4), 40: (2, 1, 2),
+}
+K3_ROWS = 5
+# 4099: a full 4096-tile (two 2048-tiles) plus 3; 3: shorter than every EPT
+K3_LENGTHS = (4099, 3, 1)
+
+
+def k3_variants(bpn):
+    """Every distinct kernel the launcher can pick for bpn: 0 is the default."""
+    default, *alts = K3_EPTS[bpn]
+    return [0] + sorted(set(alts) - {default}) + ([201, 202] if bpn <= 8 else [])
+
+
+def k3_row_stride(length, bpn):
+    from types import SimpleNamespace
+
+    from xaynet_amd.ops.base import MaskedAggregatorBase
+
+    return MaskedAggregatorBase.row_stride(SimpleNamespace(length=length, bpn=bpn))
+
+
+def k3_inputs(bpn, length, lead=0):
+    """(pool bytes [K3_ROWS, stride] after `lead` bytes, prior planes, the
+    expected planes): row 0 all 0xFF, row 1 zero, row 2 (offset mod 251) so a
+    shifted or swapped byte shows, the rest random (padding included); digit d
+    of element i is the little-endian integer of bytes [i*bpn + 4d, i*bpn +
+    min(4d + 4, bpn)), summed over the rows on top of a random accumulator."""
+    rng = np.random.default_rng(1000 * bpn + length)
+    stride = k3_row_stride(length, bpn)
+    assert stride % 16 == 0 and stride >= (length + 16) * bpn
+    flat = rng.integers(0, 256, lead + K3_ROWS * stride, dtype=np.uint8)
+    pool = flat[lead:].reshape(K3_ROWS, stride)
+    pool[0], pool[1] = 0xFF, 0
+    pool[2] = np.arange(stride) % 251
+    n_digits = (bpn + 3) // 4
+    prior = rng.integers(0, 2**40, (n_digits, length), dtype=np.uint64)
+    limbs = pool[:, : length * bpn].reshape(K3_ROWS, length, bpn).astype(np.uint64)
+    expect = prior.copy()
+    for d in range(n_digits):
+        for b in range(4 * d, min(4 * d + 4, bpn)):
+            expect[d] += (limbs[:, :, b] << np.uint64(8 * (b - 4 * d))).sum(axis=0)
+    return flat, pool, prior, expect
+
+
+def k3_config_with(bpn):
+    """A MaskConfig with that many bytes per number, if one exists."""
+    for group in (1, 0, 2):
+        for dtype in (0, 2, 3, 1):
+            for bound in (0, 2, 4, 6, 255):
+                for model in (3, 6, 9, 12):
+                    if (dtype, bound) == (1, 255):
+                        continue  # F64 Bmax: 264 bytes, beyond the planes
+                    c = mk.MaskConfig(group, dtype, bound, model)
+                    if c.bytes_per_number == bpn:
+                        return c
+    return None
+
+
+def k3_run(flat, lead, stride, prior, length, bpn, ept):
+    from xaynet_amd import _hip
+
+    dev = torch.from_numpy(flat).cuda()
+    acc = torch.from_numpy(prior.view(np.int64)).cuda()
+    assert acc.is_contiguous() and dev.numel() >= lead + K3_ROWS * stride
+    _hip.aggregate_batch(acc.data_ptr(), dev.data_ptr() + lead, stride, K3_ROWS, length, bpn, ept)
+    torch.cuda.synchronize()
+    return acc.cpu().numpy().view(np.uint64)
+
+
+@pytest.mark.parametrize("bpn", sorted(K3_EPTS))
+def test_k3_every_variant_vs_numpy(bpn):
+    """Each K3 instantiation (every EPT of every bpn, and the LDS kernels)
+    adds exactly the byte-gathered digits into a pre-filled accumulator, at a
+    full tile plus a tail and at lengths shorter than one thread's share; the
+    CPU plane agrees with the numpy reference where a config has that bpn."""
+    from xaynet_amd.ops import gpu_available
+    from xaynet_amd.ops.cpu_engine import CpuPlaneAggregator
+
+    if not gpu_available():
+        pytest.fail("GPU expected for -m gpu tests but not available")
+    cfg = k3_config_with(bpn)
+    for length in K3_LENGTHS:
+        flat, pool, prior, expect = k3_inputs(bpn, length)
+        if cfg is not None:
+            cpu = CpuPlaneAggregator(cfg, cfg, length)
+            assert cpu.row_stride() == pool.shape[1]
+            cpu.acc.copy_(torch.from_numpy(prior.view(np.int64)))
+            cpu.aggregate_pool(torch.from_numpy(pool), K3_ROWS)
+            assert (cpu.acc.numpy().view(np.uint64) == expect).all(), f"CPU plane, n={length}"
+        for ept in k3_variants(bpn):
+            got = k3_run(flat, 0, pool.shape[1], prior, length, bpn, ept)
+            bad = np.argwhere(got != expect)
+            assert bad.size == 0, (f"bpn {bpn} ept {ept} n {length}: {len(bad)} wrong, first "
+                                   f"(digit, element) {bad[:4].tolist()}")
+
+
+def test_k3_lds_request_on_misaligned_pool():
+    """ept=201 on a pool whose base is 4 bytes past a 16-byte boundary: the
+    launcher falls back to the generic kernel, with the same result."""
+    bpn, length, lead = 7, 4099, 4
+    flat, pool, prior, expect = k3_inputs(bpn, length, lead)
+    got = k3_run(flat, lead, pool.shape[1], prior, length, bpn, 201)
+    assert (got == expect).all()
+
+
 def test_k4_full_roundtrip_vs_oracle():
     length = 2000
     eng, c = make_engine(length, (1, 0, 0, 3))

@@ -89,3 +89,21 @@ def test_width_restricted_bindings():
     _hip.recode_planes(0, 0, 0, 3, WIDE_ORDER, 2, 39)
     with pytest.raises(ValueError):
         _hip.unmask_values(0, 0, HI, 0, 0, WIDE_ORDER, "1024", 0.0, 1.0, 0)
+
+
+def test_exact_offset_forms_for_u64_orders():
+    """Integer outputs of u64 orders take the exact offset and divisor through
+    both unmask bindings (len = 0: nothing is launched)."""
+    _hip.unmask(0, 0, 0, 0, 0, 2, U64_ORDER, "1024", 0.0, 1.0, 3, 32, offset="5", divisor="3")
+    _hip.unmask_values(0, 0, 0, 0, 0, U64_ORDER, "1024", 0.0, 1.0, 3, offset="5", divisor="3")
+    _hip.unmask_values(0, 0, 0, 0, 0, U64_ORDER, "1024", 0.0, 1.0, 2, offset="5")
+    with pytest.raises(ValueError):  # a divisor goes with an offset
+        _hip.unmask_values(0, 0, 0, 0, 0, U64_ORDER, "1024", 0.0, 1.0, 3, divisor="3")
+    with pytest.raises(ValueError):  # both are one word
+        _hip.unmask_values(0, 0, 0, 0, 0, U64_ORDER, "1024", 0.0, 1.0, 3, offset=str(2**64))
+    with pytest.raises(ValueError):  # the offset is below the order
+        _hip.unmask(0, 0, 0, 0, 0, 2, U64_ORDER, "1024", 0.0, 1.0, 3, 32, offset=str(2**64))
+    with pytest.raises(RuntimeError):  # float outputs of value sums keep the double kernel
+        _hip.unmask_values(0, 0, 0, 0, 0, U64_ORDER, "1024", 0.0, 1.0, 0, offset="5")
+    with pytest.raises(RuntimeError):  # integer outputs need a one-word exp_shift
+        _hip.unmask(0, 0, HI, 0, 0, 2, WIDE_ORDER, str(10**20), 0.0, 1.0, 3, 32, offset="5")

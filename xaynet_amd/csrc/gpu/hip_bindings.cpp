@@ -385,10 +385,11 @@ PYBIND11_MODULE(_hip, m) {
 
     // [n_planes][len] digit planes minus the mask -> model weights.
     // dtype follows mask::DataType: 0=F32 1=F64 2=I32 3=I64
-    // Bmax configs pass `offset` = nb * add_shift * exp_shift as a decimal
-    // string: the shift is then subtracted in integers (n_add_shift is unused),
-    // and `divisor`, where exp_shift * scalar_sum is an exact integer below
-    // 2^64, makes integer outputs the exact truncated quotient.
+    // Bmax configs, and integer outputs of the other bounds, pass `offset` =
+    // nb * add_shift * exp_shift as a decimal string: the shift is then
+    // subtracted in integers (n_add_shift is unused), and `divisor`, where
+    // exp_shift * scalar_sum is an exact integer below 2^64, makes integer
+    // outputs the exact truncated quotient.
     m.def(
         "unmask",
         [](uintptr_t planes, uintptr_t mask_lo, uintptr_t mask_hi, uintptr_t out, uint64_t len,
@@ -404,8 +405,8 @@ PYBIND11_MODULE(_hip, m) {
                                           "their exact offset");
                 if (e.n > 2) throw py::value_error("exp_shift >= 2^128 needs the exact offset");
                 if (!div.is_zero()) throw py::value_error("divisor goes with an offset");
-            } else if (o.n < 2 || off.n > o.n) {
-                throw py::value_error("the exact offset must be below the (wide) order");
+            } else if (off.n > o.n) {
+                throw py::value_error("the exact offset must be below the order");
             }
             if (div.n > 1) throw py::value_error("divisor must be below 2^64");
             // 1 / (exp_shift * scalar_sum), rounded to a double once
@@ -421,22 +422,29 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("n_add_shift"), py::arg("scalar_sum"), py::arg("dtype") = 0,
         py::arg("digit_bits") = 32, py::arg("offset") = "", py::arg("divisor") = "", nogil);
 
-    // u64 orders only: `vals` are plain u64 (cross-rank sums of) canonical values
+    // u64 orders only: `vals` are plain u64 (cross-rank sums of) canonical
+    // values. `offset` and `divisor` as for unmask, for integer outputs.
     m.def(
         "unmask_values",
         [](uintptr_t vals, uintptr_t mask_lo, uintptr_t mask_hi, uintptr_t out, uint64_t len,
            const std::string& order, const std::string& exp_shift, double n_add_shift,
-           double scalar_sum, int dtype) {
+           double scalar_sum, int dtype, const std::string& offset,
+           const std::string& divisor) {
             Limbs o = parse_order(order, mask_hi), e = parse_limbs(exp_shift);
+            Limbs off = parse_optional(offset), div = parse_optional(divisor);
             if (o.n > 1 || e.n > 1) throw py::value_error("unmask_values covers u64 orders");
+            if (off.n > 1 || div.n > 1)
+                throw py::value_error("offset and divisor must be below 2^64");
+            if (off.is_zero() && !div.is_zero())
+                throw py::value_error("divisor goes with an offset");
             check(xhip_k4_unmask_values(u64p(vals), u64p(mask_lo), dtype,
                                         reinterpret_cast<void*>(out), len, o.v.w[0], e.v.w[0],
-                                        n_add_shift, scalar_sum),
+                                        n_add_shift, scalar_sum, off.v.w[0], div.v.w[0]),
                   "k4_unmask_values");
         },
         py::arg("vals"), py::arg("mask_lo"), py::arg("mask_hi"), py::arg("out"), py::arg("len"),
         py::arg("order"), py::arg("exp_shift"), py::arg("n_add_shift"), py::arg("scalar_sum"),
-        py::arg("dtype") = 0, nogil);
+        py::arg("dtype") = 0, py::arg("offset") = "", py::arg("divisor") = "", nogil);
 
     // [n_planes][len] digit planes -> canonical values mod order
     m.def(

@@ -72,10 +72,14 @@ hipError_t xhip_k4_unmask(const uint64_t* planes, const uint64_t* mask_lo,
                           int n_planes, int digit_bits, uint64_t order_lo, uint64_t order_hi,
                           uint64_t exp_lo, uint64_t exp_hi, double n_add_shift,
                           double scalar_sum);
-// u64 orders only: unmask (cross-rank sums of) canonical values
+// u64 orders only: unmask (cross-rank sums of) canonical values. offset == 0:
+// the shift-in-doubles kernel. offset = nb * add_shift * exp_shift (integer
+// dtypes only): the exact-offset kernel of xhip_k4_unmask_limbs on one plane
+// of whole-word values, `divisor` as there.
 hipError_t xhip_k4_unmask_values(const uint64_t* vals, const uint64_t* mask, int dtype,
                                  void* out, uint64_t len, uint64_t order, uint64_t exp_shift,
-                                 double n_add_shift, double scalar_sum);
+                                 double n_add_shift, double scalar_sum, uint64_t offset,
+                                 uint64_t divisor);
 hipError_t xhip_k2_canonicalize(const uint64_t* planes, uint64_t* out_lo, uint64_t* out_hi,
                                 uint64_t len, int n_planes, int digit_bits, uint64_t order_lo,
                                 uint64_t order_hi);
@@ -123,11 +127,15 @@ hipError_t xhip_k1_scatter_compact_limbs(const uint64_t* cand_lo, const uint64_t
                                          uint64_t* out_lo, uint64_t* out_hi, uint64_t out_len,
                                          xhip_limbs order);
 // offset == 0: the shift-in-doubles unmask of the B0..B6 bounds (L <= 2,
-// exp_shift below 2^128). offset != 0 (Bmax, L = 2..5): the exact-offset
-// unmask, weight = (t - offset) / (exp_shift * scalar_sum); n_add_shift is
-// unused, `divisor` is exp_shift * scalar_sum where that is an exact integer
-// below 2^64 (else 0) and `scale` the double nearest 1/(exp_shift *
-// scalar_sum). Integer dtypes need a one-word exp_shift.
+// exp_shift below 2^128): float outputs, and integer outputs without an exact
+// divisor, which are then within 1 of the exact truncated quotient. offset =
+// nb * add_shift * exp_shift != 0 (every Bmax config, L = 2..5; B0..B6
+// integer outputs that have a divisor, L = 1..2): the exact-offset unmask,
+// weight = (t - offset) / (exp_shift * scalar_sum); n_add_shift is unused,
+// `divisor` is exp_shift * scalar_sum where that is an exact integer below
+// 2^64 (else 0) - integer outputs are then exact - and `scale` the double
+// nearest 1/(exp_shift * scalar_sum). Integer dtypes need a one-word
+// exp_shift; u64 orders (L = 1) 32-bit digits.
 hipError_t xhip_k4_unmask_limbs(const uint64_t* planes, const uint64_t* mask_lo,
                                 const uint64_t* mask_hi, int dtype, void* out, uint64_t len,
                                 int n_planes, int digit_bits, xhip_limbs order,

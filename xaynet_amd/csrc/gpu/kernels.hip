@@ -1185,11 +1185,16 @@ __global__ void k6_pack_ml(
     ml_pack_bytes<L>(out + i * bpn, bpn, ml_load<L>(in, istride, i));
 }
 
-// K4 with an exact offset, for every Bmax config (L = 2..5). There n*add_shift
-// (up to nb * 2^128) dwarfs the weights it is subtracted from, so the
-// subtraction happens in integers:
+// K4 with an exact offset: every Bmax config (L = 2..5), and the integer
+// models of the B0..B6 bounds that have an exact divisor (L = 1, 2). For Bmax
+// n*add_shift (up to nb * 2^128) dwarfs the weights it is subtracted from; for
+// B0..B6 integer models the truncation of a quotient that is itself an integer
+// cannot be decided in doubles (they land one ulp below it and truncate to the
+// integer under it). So the subtraction happens in integers:
 //   t = (planes mod order - mask) mod order,  d = t - C,  C = nb*add*E exact,
 // a signed multi-limb integer with weight = d / (E * scalar_sum).
+// L = 1 (u64 orders): `mask` is the one row of u64 values and `planes` either
+// the 32-bit digit planes or, with n_planes = 1, plain u64 value sums.
 // Integer outputs (E = 10^10, one word): with `divisor` = E * scalar_sum as an
 // exact integer the truncated quotient |d| / divisor is exact; without one
 // (divisor == 0: it is no integer or exceeds a word) the double steps of
@@ -1512,9 +1517,24 @@ hipError_t xhip_k4_unmask(const uint64_t* planes, const uint64_t* mask_lo,
 
 hipError_t xhip_k4_unmask_values(const uint64_t* vals, const uint64_t* mask, int dtype,
                                  void* out, uint64_t len, uint64_t order, uint64_t exp_shift,
-                                 double n_add_shift, double scalar_sum) {
+                                 double n_add_shift, double scalar_sum, uint64_t offset,
+                                 uint64_t divisor) {
     return dispatch_dtype(dtype, [&](auto t) {
         using OUT = typename decltype(t)::type;
+        constexpr bool TRUNC = decltype(t)::trunc;
+        if (offset) {
+            // the value sums are one plane of whole-word "digits"
+            if constexpr (TRUNC) {
+                if (!exp_shift || offset >= order) return hipErrorInvalidValue;
+                return launch_1d(k4_unmask_offset<OUT, TRUNC, 1>, len, vals, mask, int64_t(0),
+                                 static_cast<OUT*>(out), len, 1, 32,
+                                 xhip_limbs{{order, 0, 0, 0, 0}},
+                                 xhip_limbs{{offset, 0, 0, 0, 0}}, exp_shift, divisor,
+                                 scalar_sum, 0.0);
+            } else {
+                return hipErrorInvalidValue;  // float outputs keep the double steps
+            }
+        }
         return launch_1d(k4_unmask_values<OUT, decltype(t)::trunc>, len, vals, mask,
                          static_cast<OUT*>(out), len, order, exp_shift, n_add_shift,
                          scalar_sum);
@@ -1608,6 +1628,9 @@ struct LimbCount {
 template <int MIN, typename F>
 static hipError_t dispatch_limbs(int n, F f) {
     if (n < MIN) return hipErrorInvalidValue;
+    if constexpr (MIN <= 1) {
+        if (n == 1) return f(LimbCount<1>{});
+    }
     if constexpr (MIN <= 2) {
         if (n == 2) return f(LimbCount<2>{});
     }
@@ -1687,18 +1710,21 @@ hipError_t xhip_k4_unmask_limbs(const uint64_t* planes, const uint64_t* mask_lo,
                               order.w[0], order.w[1], exp_shift.w[0], exp_shift.w[1],
                               n_add_shift, scalar_sum);
     }
-    if (bad_planes_ml(n, n_planes, digit_bits) || n_limbs_of(offset) > n)
+    // u64 orders keep their 32-bit digits and have no second mask row
+    if (bad_planes_ml(n, n_planes, digit_bits) || n_limbs_of(offset) > n ||
+        (n == 1 && digit_bits != 32))
         return hipErrorInvalidValue;
     const bool exp_is_word = n_limbs_of(exp_shift) == 1 && exp_shift.w[0] != 0;
+    const int64_t mstride = n == 1 ? 0 : row_stride(mask_lo, mask_hi);
     return dispatch_dtype(dtype, [&](auto t) {
         using OUT = typename decltype(t)::type;
         constexpr bool TRUNC = decltype(t)::trunc;
         if (TRUNC && !exp_is_word) return hipErrorInvalidValue;
-        return dispatch_limbs<2>(n, [&](auto l) {
+        return dispatch_limbs<1>(n, [&](auto l) {
             return launch_1d(k4_unmask_offset<OUT, TRUNC, decltype(l)::value>, len, planes,
-                             mask_lo, row_stride(mask_lo, mask_hi), static_cast<OUT*>(out), len,
-                             n_planes, digit_bits, order, offset, exp_shift.w[0], divisor,
-                             scalar_sum, scale);
+                             mask_lo, mstride, static_cast<OUT*>(out), len, n_planes,
+                             digit_bits, order, offset, exp_shift.w[0], divisor, scalar_sum,
+                             scale);
         });
     });
 }

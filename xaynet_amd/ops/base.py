@@ -162,15 +162,19 @@ class MaskedAggregatorBase:
         mask::DataType (default: the vect config's). A Bmax unit config has
         nb*add_1 beyond the doubles that n1/exp_1 cancels against, so its
         scalar_sum = (n1 - nb*add_1*exp_1)/exp_1 is formed exactly and rounded
-        once. For a Bmax vect config the shifts carry the exact integer
-        "offset" = nb * add_shift * exp_shift that the unmask subtracts in
-        the integer domain (None otherwise), and the "divisor": with d the
-        offset-free integer, a weight is d / (exp_shift * scalar_sum) =
-        d / divisor, divisor = exp_shift * (n1 - nb*add_1*exp_1) / exp_1.
-        Integer outputs truncate that quotient, which doubles cannot decide
-        beyond ~2^40, so the divisor is handed on as an exact integer where
-        it is one and fits a u64 (the same config for both parts and scalars
-        summing to less than 2^64 / exp_shift); None otherwise."""
+        once. The shifts carry the exact integer "offset" = nb * add_shift *
+        exp_shift that the unmask can subtract in the integer domain, and the
+        "divisor": with d the offset-free integer, a weight is
+        d / (exp_shift * scalar_sum) = d / divisor, divisor = exp_shift *
+        (n1 - nb*add_1*exp_1) / exp_1. Integer outputs truncate that
+        quotient, which doubles cannot decide - beyond ~2^40 for Bmax, and at
+        any size where the quotient is itself an integer (3 participants of
+        scalar 1/3 and weight 2 give 1.9999999999963 in doubles) - so the
+        divisor is handed on as an exact integer where it is one and fits a
+        u64 (the same config for both parts and scalars summing to less than
+        2^64 / exp_shift); None otherwise. Bmax configs always unmask through
+        the offset; the other bounds do for integer outputs that have a
+        divisor (`exact_integers`)."""
         info = _cfg_scalars(self.unit_cfg)
         n1 = (self.unit_acc + int(self.unit_cfg.order) - mask_unit) % int(self.unit_cfg.order)
         exp1 = info["exp_shift_u64"]
@@ -182,11 +186,17 @@ class MaskedAggregatorBase:
             raise ZeroDivisionError("scalar_sum is zero")
         dt = self.vect_cfg.dtype if dtype is None else dtype
         vinfo = _cfg_scalars(self.vect_cfg)
-        vinfo["offset"] = vinfo["divisor"] = None
-        if self.bmax:
-            vinfo["offset"] = nb * vinfo["add_shift"] * vinfo["exp_shift_u64"]
-            div = Fraction(vinfo["exp_shift_u64"] * (n1 - nb * int(info["add_shift"]) * exp1),
-                           exp1)
-            if div.denominator == 1 and 0 < div < 2**64:
-                vinfo["divisor"] = int(div)
+        # add_shift is an integer for every bound (a float 1.0 .. 1e6 for B0..B6)
+        vinfo["offset"] = nb * int(vinfo["add_shift"]) * vinfo["exp_shift_u64"]
+        vinfo["divisor"] = None
+        div = Fraction(vinfo["exp_shift_u64"] * (n1 - nb * int(info["add_shift"]) * exp1), exp1)
+        if div.denominator == 1 and 0 < div < 2**64:
+            vinfo["divisor"] = int(div)
         return scalar_sum, vinfo, dt
+
+    def exact_integers(self, vinfo, dt: int) -> bool:
+        """Whether a B0..B6 unmask takes the exact-offset path: integer
+        outputs with an exact divisor (and the one-word exp_shift that integer
+        vect configs have). Float outputs keep the double steps."""
+        return (not self.bmax and dt in (2, 3) and vinfo["divisor"] is not None
+                and vinfo["exp_shift_u64"] < 2**64)

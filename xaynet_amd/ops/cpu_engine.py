@@ -226,16 +226,17 @@ class CpuPlaneAggregator(MaskedAggregatorBase):
         t = (masked + order - self._ints(mask_values)) % order
         exp = vinfo["exp_shift_u64"]
         n_add = nb * vinfo["add_shift"]
+        # the exact-offset K4: d = t - nb*add*E as a signed integer
+        d = [int(v) - vinfo["offset"] for v in t]
+        if dt in (2, 3) and vinfo["divisor"] and (self.bmax or self.exact_integers(vinfo, dt)):
+            # exact truncated quotient, never through doubles; the low 64
+            # bits wrap into the output type as the kernel's casts do
+            div = vinfo["divisor"]
+            exact = [-(-v // div) if v < 0 else v // div for v in d]
+            wrapped = np.array([q & _M64 for q in exact], dtype=_U64).astype(np.int64)
+            return torch.from_numpy(wrapped.astype(self._NP_DTYPES[dt]))
         if self.bmax:
-            # mirror the exact-offset K4: d = t - nb*add*E as a signed
-            # integer, then the same double steps as the kernel
-            d = [int(v) - vinfo["offset"] for v in t]
-            if dt in (2, 3) and vinfo["divisor"]:
-                # exact truncated quotient, never through doubles
-                div = vinfo["divisor"]
-                exact = [-(-v // div) if v < 0 else v // div for v in d]
-                return torch.from_numpy(np.array(exact, dtype=np.int64)
-                                        .astype(self._NP_DTYPES[dt]))
+            # no exact divisor: the same double steps as the kernel
             if dt in (2, 3):
                 outf = np.array([_bmax_int_weight(v, exp, scalar_sum) for v in d],
                                 dtype=np.float64)
@@ -243,14 +244,12 @@ class CpuPlaneAggregator(MaskedAggregatorBase):
                 scale = float(1 / (exp * Fraction(scalar_sum)))
                 outf = np.array([math.copysign(float(abs(v)) * scale, v) for v in d],
                                 dtype=np.float64)
-        elif self.wide:
-            # mirror k4_unmask_u128: double(t / E) + double(t % E) / double(E)
+        else:
+            # the double steps of k4_unmask, k4_unmask_values and
+            # k4_unmask_u128 alike: double(t / E) + double(t % E) / double(E),
+            # minus nb*add_shift, over scalar_sum
             outf = np.array([(float(int(v) // exp) + float(int(v) % exp) / float(exp) - n_add)
                              / scalar_sum for v in t], dtype=np.float64)
-        else:
-            # mirror K4: float(t)/exp_shift - nb*add_shift, then / scalar_sum
-            outf = np.array([(int(v) / exp - n_add) / scalar_sum for v in t],
-                            dtype=np.float64)
         np_dt = self._NP_DTYPES[dt]
         if dt in (2, 3):
             outf = np.trunc(outf)

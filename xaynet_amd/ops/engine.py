@@ -222,9 +222,11 @@ class GpuMaskedAggregator(MaskedAggregatorBase):
             raise ValueError("unmask_values: lengths differ")
         scalar_sum, vinfo, dt = self._unmask_scalars(mask_unit, nb_models, dtype)
         out = torch.empty(n, dtype=self._TORCH_DTYPES[dt], device=vals.device)
+        exact = self.exact_integers(vinfo, dt)
         _hip.unmask_values(v_ptr, lo, hi, out.data_ptr(), n, self.order,
                            str(vinfo["exp_shift_u64"]), nb_models * vinfo["add_shift"],
-                           scalar_sum, dt)
+                           scalar_sum, dt, offset=str(vinfo["offset"]) if exact else "",
+                           divisor=str(vinfo["divisor"]) if exact else "")
         return out
 
     def unmask_planes(self, planes: torch.Tensor, mask_values: torch.Tensor, mask_unit: int,
@@ -238,9 +240,10 @@ class GpuMaskedAggregator(MaskedAggregatorBase):
         ptr, k = self._planes(planes, n)
         scalar_sum, vinfo, dt = self._unmask_scalars(mask_unit, nb_models, dtype)
         out = torch.empty(n, dtype=self._TORCH_DTYPES[dt], device=planes.device)
-        if self.bmax:
+        if self.bmax or self.exact_integers(vinfo, dt):
             # nb*add_shift is subtracted as the exact integer offset, not as
-            # a double (which the weights would vanish against)
+            # a double: Bmax weights would vanish against it, and integer
+            # outputs of the other bounds are the exact truncated quotient
             _hip.unmask(ptr, lo, hi, out.data_ptr(), n, k, self.order,
                         str(vinfo["exp_shift_u64"]), 0.0, scalar_sum, dt, digit_bits,
                         offset=str(vinfo["offset"]), divisor=str(vinfo["divisor"] or ""))
