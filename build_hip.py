@@ -9,7 +9,10 @@ import sys
 import sysconfig
 
 
-def build(verbose=True):
+def build(verbose=True, resource_usage=False):
+    """resource_usage=True (`python build_hip.py --resource-usage`) rebuilds
+    with -Rpass-analysis=kernel-resource-usage: the compiler then reports every
+    kernel's registers, scratch and occupancy on stderr."""
     root = os.path.dirname(os.path.abspath(__file__))
     import pybind11
 
@@ -21,9 +24,9 @@ def build(verbose=True):
     out = os.path.join(root, "xaynet_amd", f"_hip{ext}")
 
     # skip if up to date (kernels.h: the C ABI both sources include)
-    deps = src + [os.path.join(root, "xaynet_amd", "csrc", "gpu", h) for h in ("kernels.h", "limbs.h", "k1_candidates_lds_body.inc",
+    deps = src + [os.path.join(root, "xaynet_amd", "csrc", "gpu", h) for h in ("kernels.h", "limbs.h", "mask_quant.h", "k1_candidates_lds_body.inc",
                         "k1_candidates_lds_u128_body.inc")]
-    if os.path.exists(out) and all(os.path.getmtime(out) > os.path.getmtime(s) for s in deps):
+    if not resource_usage and os.path.exists(out) and all(os.path.getmtime(out) > os.path.getmtime(s) for s in deps):
         if verbose:
             print(f"_hip up to date: {out}")
         return out
@@ -43,6 +46,8 @@ def build(verbose=True):
         f"-I{sysconfig.get_paths()['include']}",
         "-o", out,
     ]
+    if resource_usage:
+        cmd.append("-Rpass-analysis=kernel-resource-usage")
     if verbose:
         print(" ".join(cmd))
     subprocess.run(cmd, check=True)
@@ -50,4 +55,4 @@ def build(verbose=True):
 
 
 if __name__ == "__main__":
-    build()
+    build(resource_usage="--resource-usage" in sys.argv[1:])

@@ -51,6 +51,26 @@ static Limbs parse_optional(const std::string& dec) {
     return parse_limbs(dec);
 }
 
+// A double that is an integer in [1, 2^320) as limbs, exactly; false for any
+// other double.
+static bool integral_limbs(double x, Limbs& out) {
+    if (!(x >= 1.0) || !std::isfinite(x) || x != std::floor(x)) return false;
+    int e;
+    const double m = std::frexp(x, &e);  // x = m * 2^e, m in [0.5, 1), e >= 1
+    if (e > 64 * ML_MAX_LIMBS) return false;
+    limbs<ML_MAX_LIMBS> v = ml_zero<ML_MAX_LIMBS>();
+    v.w[0] = uint64_t(std::ldexp(m, 53));  // the 53-bit mantissa
+    if (e >= 53) {
+        ml_shl(v, e - 53);
+    } else {
+        v.w[0] >>= 53 - e;  // x is an integer: only zeros leave
+    }
+    out = Limbs{{{v.w[0], v.w[1], v.w[2], v.w[3], v.w[4]}}, 1};
+    for (int j = 1; j < ML_MAX_LIMBS; ++j)
+        if (out.v.w[j]) out.n = j + 1;
+    return true;
+}
+
 // The one width rule: an order is wide iff it is >= 2^64, and canonical
 // values are a (lo, hi) pointer pair whose hi is null exactly for u64 orders.
 // For wide orders lo and hi are limb rows 0 and 1, and row j of the order's
@@ -531,12 +551,36 @@ PYBIND11_MODULE(_hip, m) {
     // real weights (dtype as for unmask): quantize, add the mask, pack. Bmax
     // configs pass `offset` = add_shift * exp_shift as a decimal string, which
     // is then added in integers.
+    // scalar_den != 0 selects the exact kernel for every width: the scalar is
+    // the fraction scalar_num / scalar_den (both below 2^63), add_shift must
+    // be an integer, and `scalar` and `offset` are not used.
     m.def(
         "mask_weights",
         [](uintptr_t w, int dtype, uintptr_t mask_lo, uintptr_t mask_hi, uintptr_t out,
            uint64_t len, int bpn, const std::string& order, double scalar, double add_shift,
-           const std::string& exp_shift, const std::string& offset) {
+           const std::string& exp_shift, const std::string& offset, const py::int_& scalar_num,
+           const py::int_& scalar_den) {
+            const py::int_ zero(0), top = py::int_(1).attr("__lshift__")(63);
+            for (const py::int_& x : {scalar_num, scalar_den})
+                if (x < zero || x >= top)
+                    throw py::value_error("mask_weights: scalar_num and scalar_den must be "
+                                          "in [0, 2^63)");
+            const uint64_t p = scalar_num.cast<uint64_t>(), q = scalar_den.cast<uint64_t>();
+            if (p != 0 && q == 0)
+                throw py::value_error("mask_weights: scalar_num goes with scalar_den");
+            Limbs a{{{0, 0, 0, 0, 0}}, 1};
+            if (q != 0 && !integral_limbs(add_shift, a))
+                throw py::value_error("mask_weights: the exact kernel needs an integral "
+                                      "add_shift in [1, 2^320)");
+            py::gil_scoped_release release;
             Limbs o = parse_order(order, mask_hi), e = parse_limbs(exp_shift);
+            if (q != 0) {
+                check(xhip_k5_mask_weights_exact_limbs(reinterpret_cast<const void*>(w), dtype,
+                                                       u64p(mask_lo), u64p(mask_hi), u8p(out),
+                                                       len, bpn, o.v, a.v, e.v, p, q),
+                      "k5_mask_weights_exact");
+                return;
+            }
             Limbs off = parse_optional(offset);
             if (off.is_zero() ? (o.n > 2 || e.n > 2) : (o.n < 2 || off.n > o.n || e.n > o.n))
                 throw py::value_error(
@@ -549,7 +593,8 @@ PYBIND11_MODULE(_hip, m) {
         },
         py::arg("w"), py::arg("dtype"), py::arg("mask_lo"), py::arg("mask_hi"), py::arg("out"),
         py::arg("len"), py::arg("bpn"), py::arg("order"), py::arg("scalar"),
-        py::arg("add_shift"), py::arg("exp_shift"), py::arg("offset") = "", nogil);
+        py::arg("add_shift"), py::arg("exp_shift"), py::arg("offset") = "",
+        py::arg("scalar_num") = py::int_(0), py::arg("scalar_den") = py::int_(0));
 
     // canonical values <-> packed wire limbs of bpn bytes
     m.def(

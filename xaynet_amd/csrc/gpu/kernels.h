@@ -161,6 +161,14 @@ hipError_t xhip_k5_mask_weights_limbs(const void* w, int dtype, const uint64_t* 
                                       const uint64_t* mask_hi, uint8_t* out, uint64_t len,
                                       int bpn, xhip_limbs order, double scalar, double add_shift,
                                       xhip_limbs exp_shift, xhip_limbs offset);
+// Exact mode, L = 1..5: the scalar is the fraction p/q (both below 2^63,
+// already clamped to the unit config's bound), add_shift an integer, and
+// every element is quantised in integers (mask_quant.h): the output is the
+// rational masker's, byte for byte. Needs 2 * add_shift * exp_shift < order.
+hipError_t xhip_k5_mask_weights_exact_limbs(const void* w, int dtype, const uint64_t* mask_lo,
+                                            const uint64_t* mask_hi, uint8_t* out, uint64_t len,
+                                            int bpn, xhip_limbs order, xhip_limbs add_shift,
+                                            xhip_limbs exp_shift, uint64_t p, uint64_t q);
 hipError_t xhip_k6_unpack_limbs(const uint8_t* in, uint64_t* out_lo, uint64_t* out_hi,
                                 uint64_t len, int bpn, xhip_limbs order);
 hipError_t xhip_k6_pack_limbs(const uint64_t* in_lo, const uint64_t* in_hi, uint8_t* out,

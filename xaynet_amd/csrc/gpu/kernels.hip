@@ -32,6 +32,7 @@
 // kernels; the f32 and i64 Bmax configs). Only f64 Bmax orders (2112..2143
 // bits) take the CPU oracle.
 #include "kernels.h"
+#include "mask_quant.h"
 
 #define WAVE 64
 
@@ -1265,6 +1266,21 @@ __global__ void k5_mask_weights_offset(
     ml_pack_bytes<L>(out + i * bpn, bpn, val);
 }
 
+// K5w, exact mode, every width (L = 1..5): the element is quantised in
+// integers as the rational masker quantises it (mask_quant.h; the scalar is
+// the fraction p/q, the element is taken as typed), so the bytes are the ones
+// the CPU masker sends. L = 1: `mask` is the one row of u64 values.
+template <typename T, int L>
+__global__ void k5_mask_weights_exact(
+    const T* __restrict__ w, const uint64_t* __restrict__ mask, int64_t mstride,
+    uint8_t* __restrict__ out, uint64_t len, int bpn, xhip_limbs order_c, mq_params params) {
+    uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= len) return;
+    limbs<L> val = mq_quantize<L>(mq_decompose(w[i]), params);
+    ml_mod_add<L>(val, ml_load<L>(mask, mstride, i), ml_from<L>(order_c));
+    ml_pack_bytes<L>(out + i * bpn, bpn, val);
+}
+
 // ===================================================================
 // Host-side launchers (C ABI declared in kernels.h, consumed by
 // hip_bindings.cpp). All launches go to the null stream, which serializes
@@ -1827,6 +1843,26 @@ hipError_t xhip_k5_mask_weights_limbs(const void* w, int dtype, const uint64_t* 
             return launch_1d(k5_mask_weights_offset<T, decltype(l)::value>, len,
                              static_cast<const T*>(w), mask_lo, row_stride(mask_lo, mask_hi),
                              out, len, bpn, order, scalar, add_shift, exp_shift, offset);
+        });
+    });
+}
+
+hipError_t xhip_k5_mask_weights_exact_limbs(const void* w, int dtype, const uint64_t* mask_lo,
+                                            const uint64_t* mask_hi, uint8_t* out, uint64_t len,
+                                            int bpn, xhip_limbs order, xhip_limbs add_shift,
+                                            xhip_limbs exp_shift, uint64_t p, uint64_t q) {
+    const int n = n_limbs_of(order);
+    mq_params params;
+    if (bpn < 1 || bpn > 8 * n || (n > 1) != (mask_hi != nullptr) ||
+        !mq_prepare(order, n, add_shift, exp_shift, p, q, params))
+        return hipErrorInvalidValue;
+    const int64_t mstride = n == 1 ? 0 : row_stride(mask_lo, mask_hi);
+    return dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        return dispatch_limbs<1>(n, [&](auto l) {
+            return launch_1d(k5_mask_weights_exact<T, decltype(l)::value>, len,
+                             static_cast<const T*>(w), mask_lo, mstride, out, len, bpn, order,
+                             params);
         });
     });
 }

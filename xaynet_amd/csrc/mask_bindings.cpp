@@ -3,6 +3,7 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include "gpu/mask_quant.h"
 #include "mask/masking.h"
 
 namespace py = pybind11;
@@ -16,8 +17,76 @@ static MaskConfig cfg_from_ints(int g, int d, int b, int m) {
     return *c;
 }
 
+// ---- quantize_exact: the GPU's exact quantiser (gpu/mask_quant.h) on the host
+
+static bool to_limbs(const BigUint& v, xhip_limbs& out) {
+    if (v.bits() > 64 * ML_MAX_LIMBS) return false;
+    uint8_t raw[8 * ML_MAX_LIMBS];
+    v.to_bytes_le_fixed(raw, sizeof raw);
+    for (int j = 0; j < ML_MAX_LIMBS; ++j) {
+        out.w[j] = 0;
+        for (int b = 7; b >= 0; --b) out.w[j] = (out.w[j] << 8) | raw[8 * j + b];
+    }
+    return true;
+}
+
+template <typename T, int L>
+static py::list quantize_exact_as(const T* w, size_t n, const mq_params& params) {
+    py::list out;
+    for (size_t i = 0; i < n; ++i) {
+        const limbs<L> v = mq_quantize<L>(mq_decompose(w[i]), params);
+        out.append(BigUint::from_bytes_le(reinterpret_cast<const uint8_t*>(v.w), 8 * L).to_dec());
+    }
+    return out;
+}
+
+template <typename T>
+static py::list quantize_exact_typed(const py::array& weights, int L, const mq_params& params) {
+    auto a = py::array_t<T, py::array::c_style>::ensure(weights);
+    if (!a || a.ndim() != 1) throw py::value_error("weights must be a 1-D array");
+    const size_t n = size_t(a.shape(0));
+    switch (L) {
+        case 1: return quantize_exact_as<T, 1>(a.data(), n, params);
+        case 2: return quantize_exact_as<T, 2>(a.data(), n, params);
+        case 3: return quantize_exact_as<T, 3>(a.data(), n, params);
+        case 4: return quantize_exact_as<T, 4>(a.data(), n, params);
+        default: return quantize_exact_as<T, 5>(a.data(), n, params);
+    }
+}
+
+// trunc((clamp(num/den * w) + add_shift) * exp_shift) per element of `weights`
+// (taken as typed: f32, f64, i32 or i64), as decimal strings. num/den is the
+// scalar already clamped to the unit config's bound.
+static py::list quantize_exact(const py::array& weights, const MaskConfig& cfg,
+                               const py::int_& num, const py::int_& den) {
+    const py::int_ zero(0), top = py::int_(1).attr("__lshift__")(63);
+    if (num < zero || num >= top || den <= zero || den >= top)
+        throw py::value_error("quantize_exact: num in [0, 2^63) and den in [1, 2^63)");
+    const CfgInfo& ci = cfg.info();
+    const BigInt a_t = ci.add_shift.trunc();
+    xhip_limbs order, a, e;
+    mq_params params;
+    const int L = int((ci.order.bits() + 63) / 64);
+    if (a_t.neg || Rational::cmp(ci.add_shift, Rational::from_integer(a_t)) != 0 ||
+        !to_limbs(ci.order, order) || !to_limbs(a_t.mag, a) || !to_limbs(ci.exp_shift, e) ||
+        !mq_prepare(order, L, a, e, num.cast<uint64_t>(), den.cast<uint64_t>(), params))
+        throw py::value_error("quantize_exact: config outside the exact quantiser (integral "
+                              "add_shift, order below 2^320)");
+    const int tn = weights.dtype().num();  // by type number, not identity
+    if (tn == py::dtype::of<float>().num()) return quantize_exact_typed<float>(weights, L, params);
+    if (tn == py::dtype::of<double>().num())
+        return quantize_exact_typed<double>(weights, L, params);
+    if (tn == py::dtype::of<int32_t>().num())
+        return quantize_exact_typed<int32_t>(weights, L, params);
+    if (tn == py::dtype::of<int64_t>().num())
+        return quantize_exact_typed<int64_t>(weights, L, params);
+    throw py::value_error("quantize_exact: weights dtype must be f32/f64/i32/i64");
+}
+
 void bind_mask(py::module_& m) {
     auto mm = m.def_submodule("mask");
+    mm.def("quantize_exact", &quantize_exact, py::arg("weights"), py::arg("cfg"), py::arg("num"),
+           py::arg("den"));
 
     py::class_<MaskConfig>(mm, "MaskConfig")
         .def(py::init([](int g, int d, int b, int mo) { return cfg_from_ints(g, d, b, mo); }),

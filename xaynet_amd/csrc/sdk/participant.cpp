@@ -189,7 +189,7 @@ void Participant::step_update() {
                          : std::is_same_v<T, double>  ? 1
                          : std::is_same_v<T, int32_t> ? 2
                                                       : 3;
-                return mask_hook_(seed, dt, v.data(), v.size(), cfg);
+                return mask_hook_(seed, dt, v.data(), v.size(), cfg, settings_.scalar);
             },
             *local_model_);
         if (wire) {

@@ -121,10 +121,12 @@ class Participant {
     // accelerator (xaynet_amd.ops on an MI355X) instead of the CPU loops.
     // Each returns the full MaskObject wire bytes, or nullopt to fall back.
     // hooks receive the ROUND's mask config (vect,unit as (group,dtype,
-    // bound,model) codes) + model length so one accelerator serves any round
+    // bound,model) codes) + model length so one accelerator serves any round;
+    // the mask hook also receives the participant's scalar, which an exact
+    // accelerator masks with
     using MaskModelHook = std::function<std::optional<Bytes>(
         const uint8_t seed[32], int dtype, const void* data, size_t n,
-        const std::array<int, 8>& cfg)>;
+        const std::array<int, 8>& cfg, const mask::Scalar& scalar)>;
     using Sum2Hook = std::function<std::optional<Bytes>(
         const std::vector<std::array<uint8_t, 32>>& seeds, size_t length,
         const std::array<int, 8>& cfg)>;

@@ -167,17 +167,21 @@ void bind_sdk(py::module_& m) {
         .def("set_mask_model_hook",
              [](Participant& p, py::function fn) {
                  // called from tick() with the GIL released -> reacquire.
-                 // fn(seed, dtype, raw_weights, n, cfg8) -> wire bytes | None
+                 // fn(seed, dtype, raw_weights, n, cfg8, scalar_num, scalar_den)
+                 // -> wire bytes | None; the participant's scalar as Python ints
                  p.set_mask_model_hook([fn](const uint8_t seed[32], int dtype,
                                             const void* data, size_t n,
-                                            const std::array<int, 8>& cfg)
+                                            const std::array<int, 8>& cfg,
+                                            const mask::Scalar& scalar)
                                            -> std::optional<Bytes> {
                      py::gil_scoped_acquire gil;
                      size_t esz = dtype == 0 ? 4 : dtype == 2 ? 4 : 8;
                      py::bytes raw(reinterpret_cast<const char*>(data), n * esz);
                      py::tuple c = py::cast(cfg);
+                     py::object to_int = py::module_::import("builtins").attr("int");
                      py::object r = fn(py::bytes(reinterpret_cast<const char*>(seed), 32),
-                                       dtype, raw, n, c);
+                                       dtype, raw, n, c, to_int(scalar.numer.to_dec()),
+                                       to_int(scalar.denom.to_dec()));
                      if (r.is_none()) return std::nullopt;
                      std::string s = py::cast<py::bytes>(r);
                      return Bytes(s.begin(), s.end());

@@ -5,6 +5,8 @@ Usage:
     accel = ParticipantAccel()          # auto-configures per round
     accel.attach(participant)           # sets both hooks
     # or: xaynet_sdk.Participant(url, gpu=True) / spawn_participant(gpu=True)
+    # ParticipantAccel(exact=True) / spawn_participant(gpu=True, gpu_exact=True):
+    # the masked update equals the CPU masker's byte for byte
 
 The hooks receive the round's mask config + model length from the SDK and
 lazily build (and cache) one engine per (config, length). They fall back to
@@ -26,13 +28,19 @@ _NP_DTYPES = {0: np.float32, 1: np.float64, 2: np.int32, 3: np.int64}
 
 
 class ParticipantAccel:
-    def __init__(self, device: str = "cuda:0", scalar_num: int = 1, scalar_den: int = 1):
+    def __init__(self, device: str = "cuda:0", scalar_num: int = 1, scalar_den: int = 1,
+                 exact: bool = False):
+        """exact=False masks with the constructor's scalar through the
+        double-precision K5w kernel. exact=True masks with the scalar the hook
+        hands over (the participant's own) in exact mode: the update is the
+        CPU masker's, byte for byte."""
         import torch
 
         self.torch = torch
         self.device = device
         self.scalar_num = scalar_num
         self.scalar_den = scalar_den
+        self.exact = exact
         # one accelerator may be shared by many participants (threads): the
         # engines + scratch are serialized under a lock
         self._mu = threading.Lock()
@@ -55,12 +63,24 @@ class ParticipantAccel:
 
     # ---- hooks ----
 
-    def mask_model(self, seed: bytes, dtype: int, raw: bytes, n: int, cfg8):
+    def mask_model(self, seed: bytes, dtype: int, raw: bytes, n: int, cfg8,
+                   scalar_num: int | None = None, scalar_den: int | None = None):
+        """scalar_num/scalar_den: the participant's scalar, as the SDK hook
+        passes it; used in exact mode only. A scalar the exact kernel cannot
+        take (a term of 2^63 or more) gives None, the CPU fallback."""
         with self._mu:
             try:
                 eng = self._engine_for(cfg8, n)[0]
                 w = np.frombuffer(raw, dtype=_NP_DTYPES[dtype])
                 t = self.torch.from_numpy(w.copy())
+                if self.exact:
+                    if scalar_num is None or scalar_den is None:
+                        raise ValueError("exact mode needs the participant's scalar")
+                    if not (0 <= scalar_num < 2**63 and 0 < scalar_den < 2**63):
+                        LOG.info("scalar past 2^63: update masking stays on the CPU")
+                        return None
+                    return eng.mask_weights(seed, t, int(scalar_num), int(scalar_den),
+                                            exact=True)
                 return eng.mask_weights(seed, t, self.scalar_num, self.scalar_den)
             except Exception:  # noqa: BLE001 — CPU fallback
                 LOG.exception("GPU mask_model hook failed; falling back to CPU")

@@ -146,6 +146,15 @@ class MaskedAggregatorBase:
         v, _ = _core.mask.unit_draw(seed, self.unit_cfg)
         return int(v)
 
+    def clamped_scalar(self, scalar_num: int, scalar_den: int):
+        """The scalar as the masker applies it: clamped to the unit config's
+        add_shift, exactly, and reduced to lowest terms (p, q)."""
+        if scalar_num < 0 or scalar_den <= 0:
+            raise ValueError("a scalar is a non-negative fraction")
+        s = min(Fraction(scalar_num, scalar_den),
+                Fraction(int(_cfg_scalars(self.unit_cfg)["add_shift"])))
+        return s.numerator, s.denominator
+
     def masked_unit_for(self, seed: bytes, scalar_num: int, scalar_den: int) -> int:
         """Masked scalar for a synthetic update."""
         info = _cfg_scalars(self.unit_cfg)

@@ -268,21 +268,36 @@ class GpuMaskedAggregator(MaskedAggregatorBase):
                        scalar, vinfo["add_shift"], str(vinfo["exp_shift_u64"]))
 
     def mask_weights(self, seed: bytes, weights: torch.Tensor,
-                     scalar_num: int = 1, scalar_den: int = 1) -> bytes:
+                     scalar_num: int = 1, scalar_den: int = 1, exact: bool = False) -> bytes:
         """Mask a REAL weight tensor (the participant's update task): K1
         expand + K5w quantize+mask+pack; returns the full MaskObject wire
         bytes (MaskVect || MaskUnit). Replaces the CPU fast masker's hot
         loop (reference Masker::mask, masking.rs:358-404) for GPU clients.
         Quantization deviates from the exact-rational path by at most a few
-        1/exp_shift quanta (double rounding before an exact mulshift)."""
+        1/exp_shift quanta (double rounding before an exact mulshift).
+        exact=True quantises in integers instead, for every config the engine
+        covers: the bytes are the rational masker's (mask_model_oracle). The
+        scalar, clamped to the unit config's bound and reduced, must then have
+        numerator and denominator below 2^63 (ValueError otherwise)."""
         if weights.numel() != self.length:
             raise ValueError("weights length != model length")
         dt = self._WEIGHT_DTYPES[weights.dtype]
+        if exact:
+            p, q = self.clamped_scalar(scalar_num, scalar_den)
+            if p >= 2**63 or q >= 2**63:
+                raise ValueError("exact masking takes a scalar whose reduced numerator and "
+                                 "denominator are below 2^63")
         w_dev = weights.to(self.device).contiguous()
         mask_vals = self.derive_mask_values(seed)  # named: must outlive the kernel launch
         lo, hi, n = self._vals(mask_vals)
         vinfo = _cfg_scalars(self.vect_cfg)
         out = torch.empty(n * self.bpn, dtype=torch.uint8, device=self.device)
+        if exact:
+            _hip.mask_weights(w_dev.data_ptr(), dt, lo, hi, out.data_ptr(), n, self.bpn,
+                              self.order, p / q, float(vinfo["add_shift"]),
+                              str(vinfo["exp_shift_u64"]), scalar_num=p, scalar_den=q)
+            # masked_unit_for assumes scalar <= add_shift: hand it the clamped one
+            return self.wire_object(out, self.masked_unit_for(seed, p, q))
         # Bmax: add_shift (a dtype extreme, exact as a double) clamps; the
         # shift itself is added as the integer add_shift * exp_shift
         offset = str(vinfo["add_shift"] * vinfo["exp_shift_u64"]) if self.bmax else ""

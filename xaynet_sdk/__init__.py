@@ -25,14 +25,17 @@ def spawn_participant(
     state: Optional[List[int]] = None,
     scalar: float = 1.0,
     gpu: bool = False,
+    gpu_exact: bool = False,
 ):
     """Spawn an `InternalParticipant` thread and return its handle. If `state`
     is given, the participant is restored from it. `scalar` weights this
     participant's update in the aggregate (e.g. 1/number_of_samples).
     `gpu=True` runs the update-masking and sum2 mask-aggregation hot loops
-    on a visible MI355X (falls back to CPU per call on any error)."""
+    on a visible MI355X (falls back to CPU per call on any error); with
+    `gpu_exact=True` the masked update is the CPU masker's byte for byte and
+    uses this participant's `scalar`."""
     internal_participant = InternalParticipant(
-        coordinator_url, participant, args, kwargs, state, scalar, gpu=gpu
+        coordinator_url, participant, args, kwargs, state, scalar, gpu=gpu, gpu_exact=gpu_exact
     )
     internal_participant.start()
     return internal_participant
