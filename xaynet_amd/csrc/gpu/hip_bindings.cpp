@@ -403,6 +403,33 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("acc"), py::arg("updates"), py::arg("stride"), py::arg("n_updates"),
         py::arg("len"), py::arg("bpn"), py::arg("ept") = 0, nogil);
 
+    // private (tests, scripts/k3_sweep.py): the tile-streaming K3 plan (ept
+    // 401 / 402) for a row of `len` elements, and a read-bandwidth probe
+    m.def(
+        "_k3_tile_plan",
+        [](uint64_t len, int bpn, uint64_t stride) {
+            XhipK3TilePlan p;
+            xhip_k3_tile_plan(len, bpn, stride, &p);
+            py::dict d;
+            d["tile_elems"] = p.tile_elems;
+            d["depth"] = p.depth;
+            d["waves"] = p.waves;
+            d["n_tiles"] = p.n_tiles;
+            d["rem_start"] = p.rem_start;
+            d["max_byte"] = p.max_byte;
+            return d;
+        },
+        py::arg("len"), py::arg("bpn"), py::arg("stride"));
+
+    m.def(
+        "_read_ceiling",
+        [](uintptr_t src, uint64_t bytes, bool nontemporal, uintptr_t sink) {
+            check(xhip_read_ceiling(u8p(src), bytes, nontemporal,
+                                    reinterpret_cast<uint32_t*>(sink)),
+                  "read_ceiling");
+        },
+        py::arg("src"), py::arg("bytes"), py::arg("nontemporal"), py::arg("sink"), nogil);
+
     // [n_planes][len] digit planes minus the mask -> model weights.
     // dtype follows mask::DataType: 0=F32 1=F64 2=I32 3=I64
     // Bmax configs, and integer outputs of the other bounds, pass `offset` =

@@ -66,6 +66,28 @@ hipError_t xhip_k1_expand_batch(const uint32_t* keys_dev, const uint64_t* start_
 hipError_t xhip_k3_aggregate(uint64_t* acc, const uint8_t* updates, uint64_t stride,
                              uint32_t n_updates, uint64_t len, int bpn, int ept);
 
+// How the tile-streaming K3 kernel (ept 401 / 402) splits a row of `len`
+// elements: n_tiles full tiles of tile_elems elements through a ring of
+// `depth` LDS slots per wave (`waves` per workgroup), and the remainder
+// [rem_start, len), less than one tile, through plain loads in one more block
+// of the same launch. max_byte is the highest row byte offset the tile blocks
+// read, -1 if there is no tile. With n_tiles == 0 the generic kernel runs
+// alone. All zero (and -1) when bpn has no tile kernel, the stride is not a
+// multiple of 16 bytes, or the row has less than 16 bytes past its last
+// element (row_stride() pads 16 elements).
+struct XhipK3TilePlan {
+    uint32_t tile_elems, depth, waves;
+    uint64_t n_tiles, rem_start;
+    int64_t max_byte;
+};
+void xhip_k3_tile_plan(uint64_t len, int bpn, uint64_t stride, XhipK3TilePlan* plan);
+
+// Read-only bandwidth probe (scripts/k3_sweep.py --ceiling): reads `bytes`
+// (a multiple of 16, 16B-aligned) with coalesced 16-byte loads, default or
+// nontemporal; sink is one device word that is practically never written.
+hipError_t xhip_read_ceiling(const uint8_t* src, uint64_t bytes, bool nontemporal,
+                             uint32_t* sink);
+
 // ---- K2/K4: digit planes <-> canonical values, unmask ----
 hipError_t xhip_k4_unmask(const uint64_t* planes, const uint64_t* mask_lo,
                           const uint64_t* mask_hi, int dtype, void* out, uint64_t len,

@@ -34,6 +34,8 @@
 #include "kernels.h"
 #include "mask_quant.h"
 
+#include <algorithm>
+
 #define WAVE 64
 
 // ------------------------------------------------------------ ChaCha20 core
@@ -492,6 +494,183 @@ __global__ void k3_aggregate_lds(
             int e = t + k * TPB;
             if (e < nelem_tile) acc[uint64_t(d) * len + tile0 + e] += racc[k][d];
         }
+}
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+// K3 tile-streaming variant: a wave owns a tile of 64*T consecutive elements
+// and streams its TILE_BYTES of every update row through a wave-private ring
+// of D LDS slots, filled by LDS-DMA loads of 16 bytes per lane (one
+// instruction = 1 KiB contiguous, every cache line touched once). Row u+D-1 is
+// issued before row u is read, so D-1 rows stay in flight; a counted vmcnt
+// retires exactly the oldest row (every row is PIECES instructions, and no
+// other vector memory instruction sits in the loop). Only the issuing wave
+// reads its slots, so the covering vmcnt is all the ordering a read needs, and
+// lgkmcnt(0) retires a slot's reads before it is filled again: no barriers.
+// Lane l accumulates elements l + 64k of the tile, so the LDS reads are
+// lane-strided by BPN bytes and the final plane update is coalesced.
+// Requires 16B-aligned rows and n_tiles >= 1 full tiles inside [0, len); if
+// elements remain past them, the grid has one more block, block 0, which
+// sums them. AUX is the load's cache policy (0 default, 2 nontemporal).
+template <int BPN, int T, int D, int WAVES, int AUX>
+__global__ __launch_bounds__(WAVES * 64) void k3_aggregate_tile(
+    uint64_t* __restrict__ acc, const uint8_t* __restrict__ updates, uint64_t stride,
+    uint32_t n_updates, uint64_t len, uint32_t n_tiles) {
+    constexpr int NDIG = (BPN + 3) / 4;
+    constexpr int NW = (BPN + 6) / 4;  // words an element can straddle
+    constexpr int TILE_BYTES = 64 * T * BPN;
+    constexpr int PIECES = TILE_BYTES / 1024;
+    // +4 words: the word after an element's last may be read (and masked off)
+    constexpr int SLOT_WORDS = TILE_BYTES / 4 + 4;
+    static_assert(TILE_BYTES % 1024 == 0, "a tile is whole 1-KiB pieces");
+    static_assert(D >= 2 && PIECES * (D - 1) <= 63, "vmcnt is a 6-bit count");
+    static_assert(AUX == 0 || AUX == 2, "default or nontemporal");
+    __shared__ __attribute__((aligned(16))) uint32_t ring[WAVES * D * SLOT_WORDS];
+
+    const uint64_t rem_start = uint64_t(n_tiles) * (64 * T);
+    const bool has_rem = rem_start < len;  // then block 0 is the remainder block
+    if (has_rem && blockIdx.x == 0) {
+        // Elements [rem_start, len), fewer than one tile: thread t sums
+        // elements rem_start + t + k*blockDim over all rows with plain dword
+        // loads (rows are 16B-aligned and padded past their last element). A
+        // launch of its own would cost n_updates load latencies in series after
+        // the tiles are done; here they run beside the tile blocks.
+        constexpr int KR = (T + WAVES - 1) / WAVES;
+        uint64_t rr[KR][NDIG];
+#pragma unroll
+        for (int k = 0; k < KR; ++k)
+#pragma unroll
+            for (int d = 0; d < NDIG; ++d) rr[k][d] = 0;
+        const uint64_t b0 = (rem_start + threadIdx.x) * BPN;  // + k*64*WAVES*BPN: same shift
+        const uint32_t sh = uint32_t(b0) & 3;
+        for (uint32_t u = 0; u < n_updates; ++u) {
+            const uint32_t* r =
+                reinterpret_cast<const uint32_t*>(updates + uint64_t(u) * stride) + (b0 >> 2);
+#pragma unroll
+            for (int k = 0; k < KR; ++k) {
+                if (rem_start + threadIdx.x + k * (64 * WAVES) >= len) continue;
+                uint32_t w[NW];
+#pragma unroll
+                for (int j = 0; j < NW; ++j) w[j] = r[k * (16 * WAVES * BPN) + j];
+#pragma unroll
+                for (int d = 0; d < NDIG; ++d) {
+                    const int nb = (BPN - 4 * d) >= 4 ? 4 : (BPN - 4 * d);
+                    uint32_t val =
+                        __builtin_amdgcn_alignbyte(d + 1 < NW ? w[d + 1] : 0u, w[d], sh);
+                    if (nb < 4) val &= (1u << (8 * nb)) - 1;
+                    rr[k][d] += uint64_t(val);
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < KR; ++k) {
+            const uint64_t e = rem_start + threadIdx.x + k * (64 * WAVES);
+            if (e >= len) continue;
+#pragma unroll
+            for (int d = 0; d < NDIG; ++d) acc[uint64_t(d) * len + e] += rr[k][d];
+        }
+        return;
+    }
+
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t tile = (blockIdx.x - uint32_t(has_rem)) * WAVES + wave;
+    if (tile >= n_tiles) return;  // whole wave; there is no barrier below
+
+    uint32_t* const wring = ring + wave * (D * SLOT_WORDS);
+    const uint8_t* const src = updates + uint64_t(tile) * TILE_BYTES + lane * 16;
+    // element l + 64k starts at byte l*BPN + 64k*BPN of the tile: the shift
+    // inside its first word is the same for every k
+    const uint32_t rword = (lane * BPN) >> 2, rsh = (lane * BPN) & 3;
+
+    uint64_t racc[T][NDIG];
+#pragma unroll
+    for (int k = 0; k < T; ++k)
+#pragma unroll
+        for (int d = 0; d < NDIG; ++d) racc[k][d] = 0;
+
+    auto issue = [&](uint32_t u, uint32_t slot) {
+        const uint8_t* g = src + uint64_t(u) * stride;
+        uint32_t* l = wring + slot * SLOT_WORDS;
+#pragma unroll
+        for (int p = 0; p < PIECES; ++p) {
+            auto gp = (const __attribute__((address_space(1))) void*)(g + p * 1024);
+            auto lp = (__attribute__((address_space(3))) void*)(l + p * 256);
+            // the policy must be a literal constant
+            if constexpr (AUX == 0)
+                __builtin_amdgcn_global_load_lds(gp, lp, 16, 0, 0);
+            else
+                __builtin_amdgcn_global_load_lds(gp, lp, 16, 0, 2);
+        }
+    };
+    auto consume = [&](uint32_t slot) {
+        const uint32_t* r = wring + slot * SLOT_WORDS + rword;
+#pragma unroll
+        for (int k = 0; k < T; ++k) {
+            uint32_t w[NW];
+#pragma unroll
+            for (int j = 0; j < NW; ++j) w[j] = r[k * 16 * BPN + j];
+#pragma unroll
+            for (int d = 0; d < NDIG; ++d) {
+                const int nb = (BPN - 4 * d) >= 4 ? 4 : (BPN - 4 * d);
+                uint32_t val = __builtin_amdgcn_alignbyte(d + 1 < NW ? w[d + 1] : 0u, w[d], rsh);
+                if (nb < 4) val &= (1u << (8 * nb)) - 1;
+                racc[k][d] += uint64_t(val);
+            }
+        }
+    };
+    auto next = [](uint32_t slot) { return slot + 1 == D ? 0u : slot + 1; };
+
+    uint32_t wslot = 0, rslot = 0, u = 0;
+    for (; u < n_updates && u < D - 1; ++u) {  // prologue: rows 0..D-2
+        issue(u, wslot);
+        wslot = next(wslot);
+    }
+    for (u = 0; u + (D - 1) < n_updates; ++u) {
+        // the slot about to be filled was read one row ago
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        issue(u + (D - 1), wslot);
+        wslot = next(wslot);
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PIECES * (D - 1)) : "memory");
+        consume(rslot);
+        rslot = next(rslot);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // drain: the last D-1 rows
+    for (; u < n_updates; ++u) {
+        consume(rslot);
+        rslot = next(rslot);
+    }
+
+    const uint64_t e0 = uint64_t(tile) * (64 * T) + lane;
+#pragma unroll
+    for (int d = 0; d < NDIG; ++d)
+#pragma unroll
+        for (int k = 0; k < T; ++k) acc[uint64_t(d) * len + e0 + 64 * k] += racc[k][d];
+}
+
+// Read-only ceiling probe for K3 sweeps: every lane reads 16 bytes per load,
+// a wave 1 KiB contiguous, a block 32 KiB; the XOR of the words keeps the
+// loads alive (the store practically never happens).
+template <bool NT>
+__global__ void k_read_ceiling(const u32x4* __restrict__ src, uint64_t n_vec,
+                               uint32_t* __restrict__ sink) {
+    uint64_t i0 = uint64_t(blockIdx.x) * 2048 + threadIdx.x;
+    u32x4 x = {0, 0, 0, 0};
+    if (uint64_t(blockIdx.x) * 2048 + 2048 <= n_vec) {  // all 8 loads in flight
+        u32x4 v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            v[k] = NT ? __builtin_nontemporal_load(&src[i0 + k * 256]) : src[i0 + k * 256];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) x ^= v[k];
+    } else {
+        for (int k = 0; k < 8; ++k) {
+            uint64_t i = i0 + k * 256;
+            if (i < n_vec) x ^= NT ? __builtin_nontemporal_load(&src[i]) : src[i];
+        }
+    }
+    uint32_t r = x.x ^ x.y ^ x.z ^ x.w;
+    if (r == 0x9e3779b9u && (x.x + x.y) == 0x7f4a7c15u) sink[0] = r;
 }
 
 // ---------------------------------------- K4: finalize + unmask (u64 orders)
@@ -1409,9 +1588,69 @@ hipError_t xhip_k1_expand_batch(const uint32_t* keys_dev, const uint64_t* start_
 
 // ---- K3 ----
 
+// The tile kernel's shape per bytes-per-number: X(BPN, T, D, WAVES). T is the
+// smallest value >= 4 with T*BPN % 16 == 0 (whole 1-KiB pieces per tile); D
+// and WAVES are the measured choice (profiles/r10_k3_tile.md). A bpn without
+// a line has no tile kernel.
+#define K3_TILE_CONFIGS(X)                                                                      \
+    X(3, 16, 3, 4)                                                                              \
+    X(7, 16, 3, 4)                                                                              \
+    X(10, 8, 3, 4)                                                                              \
+    X(18, 8, 2, 4)                                                                              \
+    X(40, 4, 2, 4)
+
+void xhip_k3_tile_plan(uint64_t len, int bpn, uint64_t stride, XhipK3TilePlan* plan) {
+    *plan = XhipK3TilePlan{0, 0, 0, 0, 0, -1};
+    uint32_t t = 0, d = 0, waves = 0;
+#define K3_TILE_ROW(BPN, T, D, WAVES)                                                           \
+    if (bpn == BPN) t = T, d = D, waves = WAVES;
+    K3_TILE_CONFIGS(K3_TILE_ROW)
+#undef K3_TILE_ROW
+    // rows keep every 16-byte load aligned, and hold len elements plus the 16
+    // bytes of padding the remainder block's last word may reach into
+    if (t == 0 || stride % 16 != 0 || stride < 16 || len > (stride - 16) / uint64_t(bpn)) return;
+    plan->tile_elems = 64 * t;
+    plan->depth = d;
+    plan->waves = waves;
+    plan->n_tiles = std::min<uint64_t>(len / plan->tile_elems, 0x7fffffffu);
+    plan->rem_start = plan->n_tiles * plan->tile_elems;
+    if (plan->n_tiles) plan->max_byte = int64_t(plan->rem_start * uint64_t(bpn)) - 1;
+}
+
 hipError_t xhip_k3_aggregate(uint64_t* acc, const uint8_t* updates, uint64_t stride,
                              uint32_t n_updates, uint64_t len, int bpn, int ept) {
     uint32_t threads = 256;
+    // ept<=0 is the measured default: the tile kernel with nontemporal loads
+    // where it beat the generic kernel in the benchmark, which is bpn 7 only
+    // (profiles/r10_k3_tile.md)
+    if (ept <= 0 && bpn == 7) ept = 401;
+    // ept=401/402: tile-streaming kernel (nontemporal / default loads) where
+    // the row has a full tile; needs 16B-aligned rows
+    if (ept == 401 || ept == 402) {
+        XhipK3TilePlan plan;
+        xhip_k3_tile_plan(len, bpn, stride, &plan);
+        if (plan.n_tiles && reinterpret_cast<uintptr_t>(updates) % 16 == 0) {
+            // one block more for the elements past the last full tile
+            const uint64_t blocks_extra = plan.rem_start < len ? 1 : 0;
+#define K3_TILE_CASE(BPN, T, D, WAVES)                                                          \
+    case BPN: {                                                                                 \
+        dim3 grid(ceil_div_u32(plan.n_tiles, WAVES) + blocks_extra), block(WAVES * 64);         \
+        if (ept == 401)                                                                         \
+            hipLaunchKernelGGL((k3_aggregate_tile<BPN, T, D, WAVES, 2>), grid, block, 0, 0,     \
+                               acc, updates, stride, n_updates, len, uint32_t(plan.n_tiles));   \
+        else                                                                                    \
+            hipLaunchKernelGGL((k3_aggregate_tile<BPN, T, D, WAVES, 0>), grid, block, 0, 0,     \
+                               acc, updates, stride, n_updates, len, uint32_t(plan.n_tiles));   \
+        return hipGetLastError();                                                               \
+    }
+            switch (bpn) {
+                K3_TILE_CONFIGS(K3_TILE_CASE)
+                default:;
+            }
+#undef K3_TILE_CASE
+        }
+        ept = 0;  // no full tile, no tile kernel or misaligned rows: generic kernel
+    }
 #define K3_LAUNCH(BPN, EPT)                                                                     \
     {                                                                                           \
         uint32_t wgs = ceil_div_u32((len + EPT - 1) / EPT, threads);                            \
@@ -1493,6 +1732,21 @@ hipError_t xhip_k3_aggregate(uint64_t* acc, const uint8_t* updates, uint64_t str
     }
 #undef K3_CASE
 #undef K3_LAUNCH
+    return hipGetLastError();
+}
+
+hipError_t xhip_read_ceiling(const uint8_t* src, uint64_t bytes, bool nontemporal,
+                             uint32_t* sink) {
+    if (reinterpret_cast<uintptr_t>(src) % 16 || bytes % 16) return hipErrorInvalidValue;
+    const uint64_t n_vec = bytes / 16;
+    if (n_vec == 0 || n_vec / 2048 >= 0x7fffffffu) return hipErrorInvalidValue;
+    dim3 grid(uint32_t((n_vec + 2047) / 2048)), block(256);
+    if (nontemporal)
+        hipLaunchKernelGGL(k_read_ceiling<true>, grid, block, 0, 0,
+                           reinterpret_cast<const u32x4*>(src), n_vec, sink);
+    else
+        hipLaunchKernelGGL(k_read_ceiling<false>, grid, block, 0, 0,
+                           reinterpret_cast<const u32x4*>(src), n_vec, sink);
     return hipGetLastError();
 }
 
