@@ -18,7 +18,9 @@
 //    adds, which (a) needs no per-add carry chains and (b) makes cross-GPU
 //    reduction a plain RCCL int64 sum over xGMI (mod-order correction happens
 //    once, in the finalize kernel). Headroom: digits < 2^32, so 2^31 updates
-//    fit before overflow (>> the 10^12 protocol cap per round per config).
+//    fit one accumulator before a plane entry could pass 2^63. That is BELOW
+//    the 10^12 models of the M12 cap, so the engines enforce it:
+//    aggregate_pool refuses the update that would cross it (ops/base.py).
 //  * ChaCha20 rejection sampling is parallelized exactly: the reference
 //    stream consumes ceil(nbytes/4) keystream words per draw attempt
 //    (rand_core word-granular fill), so attempt k occupies a fixed word
@@ -33,6 +35,7 @@
 // bits) take the CPU oracle.
 #include "kernels.h"
 #include "mask_quant.h"
+#include "u192.h"
 
 #include <algorithm>
 
@@ -837,77 +840,8 @@ extern "C" __global__ void k_add_rows_u64_to_planes(
 // reductions use binary shift-subtract over a 5x64-bit window — a few
 // hundred simple ALU ops per element, executed once per round.
 
-struct u192 {
-    uint64_t w[3];  // little-endian
-};
-
-__device__ __forceinline__ void u192_shl1(u192& a) {
-    a.w[2] = (a.w[2] << 1) | (a.w[1] >> 63);
-    a.w[1] = (a.w[1] << 1) | (a.w[0] >> 63);
-    a.w[0] <<= 1;
-}
-
-__device__ __forceinline__ bool u192_geq(const u192& a, const u192& b) {
-    if (a.w[2] != b.w[2]) return a.w[2] > b.w[2];
-    if (a.w[1] != b.w[1]) return a.w[1] > b.w[1];
-    return a.w[0] >= b.w[0];
-}
-
-__device__ __forceinline__ void u192_sub(u192& a, const u192& b) {
-    unsigned __int128 d0 = (unsigned __int128)a.w[0] - b.w[0];
-    unsigned __int128 d1 = (unsigned __int128)a.w[1] - b.w[1] - ((d0 >> 64) ? 1 : 0);
-    a.w[0] = uint64_t(d0);
-    a.w[2] = a.w[2] - b.w[2] - ((d1 >> 64) ? 1 : 0);
-    a.w[1] = uint64_t(d1);
-}
-
-// value (from <=4 digit planes, < 2^160) mod order (u128, > 2^64):
-// classic binary shift-subtract. Bounded by ~96 iterations.
-__device__ __forceinline__ unsigned __int128 u192_mod_u128(u192 v, unsigned __int128 order) {
-    u192 m{{uint64_t(order), uint64_t(order >> 64), 0}};
-    int shift = 0;
-    // grow m while (m << 1) <= v (m stays below 2^191 by the loop guard)
-    while (!(m.w[2] >> 62)) {
-        u192 m2 = m;
-        u192_shl1(m2);
-        if (!u192_geq(v, m2)) break;  // m2 > v
-        m = m2;
-        ++shift;
-    }
-    for (; shift >= 0; --shift) {
-        if (u192_geq(v, m)) u192_sub(v, m);
-        m.w[0] = (m.w[0] >> 1) | (m.w[1] << 63);
-        m.w[1] = (m.w[1] >> 1) | (m.w[2] << 63);
-        m.w[2] >>= 1;
-    }
-    return ((unsigned __int128)v.w[1] << 64) | v.w[0];
-}
-
-// Recombine `n_planes` digit planes (plane stride `len`) into one u192:
-// v = sum_d plane[d][i] << (digit_bits * d), built top-down as
-// v = (v << digit_bits) + plane[d][i] with carry. digit_bits is 1..63; the
-// planes hold plain integer SUMS of digits, so a plane entry may exceed
-// 2^digit_bits. The caller guarantees the total stays inside the u192_mod_u128
-// window (accumulator: < 2^160; cross-rank compact planes: < world * order).
-// DB is the compile-time digit width (32 for the accumulator), 0 = runtime.
-template <int DB>
-__device__ __forceinline__ u192 u192_from_planes(const uint64_t* __restrict__ planes,
-                                                 uint64_t len, uint64_t i, int n_planes,
-                                                 int digit_bits) {
-    const int s = DB ? DB : digit_bits;
-    u192 v{{0, 0, 0}};
-    for (int d = n_planes - 1; d >= 0; --d) {
-        v.w[2] = (v.w[2] << s) | (v.w[1] >> (64 - s));
-        v.w[1] = (v.w[1] << s) | (v.w[0] >> (64 - s));
-        v.w[0] = (v.w[0] << s);
-        unsigned __int128 t = (unsigned __int128)v.w[0] + planes[uint64_t(d) * len + i];
-        v.w[0] = uint64_t(t);
-        if (t >> 64) {  // carry
-            if (++v.w[1] == 0) ++v.w[2];
-        }
-    }
-    return v;
-}
+// u192, u192_mod_u128, u192_from_planes<DB> and u128_digit: u192.h (shared
+// with the host instantiation the CPU tests run).
 
 // digit planes -> canonical split u64 planes mod order
 template <int DB>
@@ -922,14 +856,6 @@ __global__ void k2_canonicalize_u128(
     unsigned __int128 r = u192_mod_u128(v, order);
     out_lo[i] = uint64_t(r);
     out_hi[i] = uint64_t(r >> 64);
-}
-
-// Digit j (digit_bits wide) of a u128 value; digits may straddle the lo/hi
-// word boundary. Shifts of 128 or more (k * digit_bits may overshoot) are 0.
-__device__ __forceinline__ uint64_t u128_digit(unsigned __int128 v, int j, int digit_bits) {
-    int sh = digit_bits * j;
-    if (sh >= 128) return 0;
-    return uint64_t(v >> sh) & ((uint64_t(1) << digit_bits) - 1);
 }
 
 // canonical split lo/hi values -> ADD into k planes of digit_bits-wide digits
@@ -1760,6 +1686,21 @@ static bool bad_planes(bool wide, int n_planes, int digit_bits) {
     return wide ? digit_bits < 1 || digit_bits > 63 : digit_bits != 32;
 }
 
+// Plane windows of the kernels that READ planes back into one integer: the
+// recombined value, top plane entry (a sum below 2^64) included, must stay
+// under the 2^(64*(L+1) - 1) that ml_mod (L limbs) and u192_mod_u128 (L = 2)
+// take.
+static bool outside_window(int n_limbs, int n_planes, int digit_bits) {
+    return int64_t(n_planes - 1) * digit_bits + 64 > 64 * (n_limbs + 1) - 1;
+}
+
+// the u128 kernels' 192-bit window; u64 orders bring the one or two 32-bit
+// planes of their bytes (the engine checks the count)
+static bool bad_read_planes(bool wide, int n_planes, int digit_bits) {
+    return bad_planes(wide, n_planes, digit_bits) ||
+           (wide && outside_window(2, n_planes, digit_bits));
+}
+
 static double u128_to_double(uint64_t lo, uint64_t hi) {
     return double(((unsigned __int128)hi << 64) | lo);  // one rounding
 }
@@ -1770,7 +1711,8 @@ hipError_t xhip_k4_unmask(const uint64_t* planes, const uint64_t* mask_lo,
                           uint64_t exp_lo, uint64_t exp_hi, double n_add_shift,
                           double scalar_sum) {
     const bool wide = order_hi != 0;
-    if (bad_planes(wide, n_planes, digit_bits) || (!wide && exp_hi)) return hipErrorInvalidValue;
+    if (bad_read_planes(wide, n_planes, digit_bits) || (!wide && exp_hi))
+        return hipErrorInvalidValue;
     return dispatch_dtype(dtype, [&](auto t) {
         using OUT = typename decltype(t)::type;
         constexpr bool TRUNC = decltype(t)::trunc;
@@ -1815,7 +1757,7 @@ hipError_t xhip_k2_canonicalize(const uint64_t* planes, uint64_t* out_lo, uint64
                                 uint64_t len, int n_planes, int digit_bits, uint64_t order_lo,
                                 uint64_t order_hi) {
     const bool wide = order_hi != 0;
-    if (bad_planes(wide, n_planes, digit_bits)) return hipErrorInvalidValue;
+    if (bad_read_planes(wide, n_planes, digit_bits)) return hipErrorInvalidValue;
     if (!wide) return launch_1d(k2_canonicalize, len, planes, out_lo, len, n_planes, order_lo);
     return launch_1d(digit_bits == 32 ? k2_canonicalize_u128<32> : k2_canonicalize_u128<0>, len,
                      planes, out_lo, out_hi, len, n_planes, digit_bits, order_lo, order_hi);
@@ -1830,7 +1772,7 @@ hipError_t xhip_add_to_planes(uint64_t* planes, const uint64_t* lo, const uint64
 
 hipError_t xhip_k2_recode_planes(const uint64_t* acc, uint64_t* out, uint64_t len, int n_digits,
                                  uint64_t order_lo, uint64_t order_hi, int k, int digit_bits) {
-    if (order_hi == 0 || bad_planes(true, k, digit_bits) || n_digits < 1)
+    if (order_hi == 0 || bad_planes(true, k, digit_bits) || bad_read_planes(true, n_digits, 32))
         return hipErrorInvalidValue;
     return launch_1d(k2_recode_planes_u128, len, acc, out, len, n_digits, order_lo, order_hi, k,
                      digit_bits);
@@ -1912,11 +1854,10 @@ static hipError_t dispatch_limbs(int n, F f) {
     }
 }
 
-// Multi-limb plane windows: the recombined integer, top plane entry (a sum
-// below 2^64) included, must stay under the 2^(64*(L+1) - 1) that ml_mod takes.
+// Multi-limb plane windows (outside_window above)
 static bool bad_planes_ml(int n_limbs, int n_planes, int digit_bits) {
     if (n_planes < 1 || digit_bits < 1 || digit_bits > 63) return true;
-    return int64_t(n_planes - 1) * digit_bits + 64 > 64 * (n_limbs + 1) - 1;
+    return outside_window(n_limbs, n_planes, digit_bits);
 }
 
 // element distance between limb rows 0 and 1

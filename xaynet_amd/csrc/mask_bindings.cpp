@@ -4,6 +4,7 @@
 #include <pybind11/stl.h>
 
 #include "gpu/mask_quant.h"
+#include "gpu/u192.h"
 #include "mask/masking.h"
 
 namespace py = pybind11;
@@ -83,8 +84,91 @@ static py::list quantize_exact(const py::array& weights, const MaskConfig& cfg,
     throw py::value_error("quantize_exact: weights dtype must be f32/f64/i32/i64");
 }
 
+// ---- planes_mod: the finalize kernels' plane recombination and reduction
+// (gpu/limbs.h, gpu/u192.h) on the host
+
+static py::object int_from_limbs(const uint64_t* w, int n) {
+    const py::object from_bytes = py::module_::import("builtins").attr("int").attr("from_bytes");
+    uint8_t raw[8 * ML_MAX_LIMBS];
+    for (int j = 0; j < n; ++j)
+        for (int b = 0; b < 8; ++b) raw[8 * j + b] = uint8_t(w[j] >> (8 * b));
+    return from_bytes(py::bytes(reinterpret_cast<const char*>(raw), size_t(8 * n)), "little");
+}
+
+template <int L>
+static py::list planes_mod_ml(const uint64_t* planes, uint64_t n, int k, int digit_bits,
+                              const xhip_limbs& order) {
+    py::list out;
+    for (uint64_t i = 0; i < n; ++i) {
+        const limbs<L> r =
+            ml_mod<L>(ml_from_planes<L + 1>(planes, n, i, k, digit_bits), ml_from<L>(order));
+        out.append(int_from_limbs(r.w, L));
+    }
+    return out;
+}
+
+template <int DB>
+static py::list planes_mod_u192(const uint64_t* planes, uint64_t n, int k, int digit_bits,
+                                const xhip_limbs& order) {
+    const unsigned __int128 o = ((unsigned __int128)order.w[1] << 64) | order.w[0];
+    py::list out;
+    for (uint64_t i = 0; i < n; ++i) {
+        const unsigned __int128 r =
+            u192_mod_u128(u192_from_planes<DB>(planes, n, i, k, digit_bits), o);
+        const uint64_t w[2] = {uint64_t(r), uint64_t(r >> 64)};
+        out.append(int_from_limbs(w, 2));
+    }
+    return out;
+}
+
+// sum_d planes[d][i] << (digit_bits * d) mod order for every column i of a
+// uint64 [k, n] array. path "ml": ml_mod<L>(ml_from_planes<L + 1>) at the
+// order's limb count L = 1..5, the arithmetic of the *_ml kernels and of
+// k4_unmask_offset; path "u192": u192_mod_u128(u192_from_planes<32 or 0>),
+// the *_u128 kernels (L = 2 only; digit_bits 32 takes the compile-time
+// shift). `runtime_shift` forces <0> at 32 bits too. The plane shape must lie
+// inside the window the launchers check: (k - 1) * digit_bits + 64 <=
+// 64 * (L + 1) - 1.
+static py::list planes_mod(const py::array& planes, const py::int_& order, int digit_bits,
+                           const std::string& path, bool runtime_shift) {
+    auto a = py::array_t<uint64_t, py::array::c_style>::ensure(planes);
+    if (!a || a.ndim() != 2 || !planes.dtype().is(py::dtype::of<uint64_t>()))
+        throw py::value_error("planes_mod: planes must be a uint64 [k, n] array");
+    const int k = int(a.shape(0));
+    const uint64_t n = uint64_t(a.shape(1));
+    const int bits = order.attr("bit_length")().cast<int>();
+    if (order < py::int_(1) || bits > 64 * ML_MAX_LIMBS)
+        throw py::value_error("planes_mod: order in [1, 2^320)");
+    const int L = (bits + 63) / 64;
+    if (k < 1 || digit_bits < 1 || digit_bits > 63 ||
+        int64_t(k - 1) * digit_bits + 64 > 64 * (L + 1) - 1)
+        throw py::value_error("planes_mod: plane shape outside the reduction window");
+    xhip_limbs o;
+    const std::string raw = order.attr("to_bytes")(8 * ML_MAX_LIMBS, "little").cast<std::string>();
+    for (int j = 0; j < ML_MAX_LIMBS; ++j) {
+        o.w[j] = 0;
+        for (int b = 7; b >= 0; --b) o.w[j] = (o.w[j] << 8) | uint8_t(raw[8 * j + b]);
+    }
+    if (path == "u192") {
+        if (L != 2) throw py::value_error("planes_mod: the u192 path covers two-limb orders");
+        return digit_bits == 32 && !runtime_shift
+                   ? planes_mod_u192<32>(a.data(), n, k, digit_bits, o)
+                   : planes_mod_u192<0>(a.data(), n, k, digit_bits, o);
+    }
+    if (path != "ml") throw py::value_error("planes_mod: path is \"ml\" or \"u192\"");
+    switch (L) {
+        case 1: return planes_mod_ml<1>(a.data(), n, k, digit_bits, o);
+        case 2: return planes_mod_ml<2>(a.data(), n, k, digit_bits, o);
+        case 3: return planes_mod_ml<3>(a.data(), n, k, digit_bits, o);
+        case 4: return planes_mod_ml<4>(a.data(), n, k, digit_bits, o);
+        default: return planes_mod_ml<5>(a.data(), n, k, digit_bits, o);
+    }
+}
+
 void bind_mask(py::module_& m) {
     auto mm = m.def_submodule("mask");
+    mm.def("planes_mod", &planes_mod, py::arg("planes"), py::arg("order"), py::arg("digit_bits"),
+           py::arg("path") = "ml", py::arg("runtime_shift") = false);
     mm.def("quantize_exact", &quantize_exact, py::arg("weights"), py::arg("cfg"), py::arg("num"),
            py::arg("den"));
 

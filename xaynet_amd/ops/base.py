@@ -10,6 +10,12 @@ from xaynet_amd import _core
 
 MAX_BYTES_PER_NUMBER = 40  # group orders below 2^320: up to five u64 limbs
 
+# Updates one accumulator takes before its modular reduction: a plane entry is
+# a sum of 32-bit digits, and 2^31 * (2^32 - 1) still fits the int64 planes
+# (and the int64 collectives that sum them). Below the 10^12 models of the M12
+# cap, so aggregate_pool enforces it.
+MAX_UPDATES_PER_ACCUMULATOR = 2**31
+
 # Bmax shifts per mask::DataType (csrc/mask/config.cpp, compute_exp_exponent
 # and compute_add_shift): the clamp bound is the data type's own extreme.
 _BMAX_SHIFTS = {
@@ -84,6 +90,30 @@ class MaskedAggregatorBase:
         self.acc.zero_()
         self.nb_models = 0
         self.unit_acc = 0
+
+    def _check_headroom(self, n_updates: int):
+        """Before aggregate_pool touches the planes: the accumulator holds at
+        most MAX_UPDATES_PER_ACCUMULATOR updates."""
+        if n_updates < 0:
+            raise ValueError("n_updates is negative")
+        if self.nb_models + n_updates > MAX_UPDATES_PER_ACCUMULATOR:
+            raise OverflowError(
+                f"{self.nb_models} + {n_updates} updates exceed the 2^31 an accumulator's "
+                "digit planes hold; reduce (canonical / unmask) and reset first")
+
+    def plane_window_ok(self, k: int, digit_bits: int) -> bool:
+        """Whether [k, n] planes of digit_bits-wide digit sums can be read back
+        into one integer: with entries up to 2^64 the total is below
+        2^((k-1)*digit_bits + 64), and the reduction mod order runs in a
+        window of n_limbs + 1 words whose top bit stays clear."""
+        return (k - 1) * digit_bits + 64 <= 64 * (self.n_limbs + 1) - 1
+
+    def _check_window(self, k: int, digit_bits: int):
+        if k < 1 or not self.plane_window_ok(k, digit_bits):
+            raise ValueError(
+                f"[{k}, n] planes of {digit_bits}-bit digits can spell 2^"
+                f"{(k - 1) * digit_bits + 64}, outside the {64 * (self.n_limbs + 1) - 1}-bit "
+                "window their reduction mod order takes")
 
     def new_values(self, n: int | None = None, zero: bool = False) -> torch.Tensor:
         """A canonical value tensor for n (default: length) elements: int64

@@ -143,6 +143,7 @@ class CpuPlaneAggregator(MaskedAggregatorBase):
     # ---------------- aggregation ----------------
 
     def aggregate_pool(self, pool: torch.Tensor, n_updates: int, unit_sum: int = 0):
+        self._check_headroom(n_updates)
         rows = pool[:n_updates].numpy()
         acc = self.acc.numpy().view(_U64)
         if self.wide:
@@ -167,6 +168,7 @@ class CpuPlaneAggregator(MaskedAggregatorBase):
     def _planes_to_ints(self, planes: torch.Tensor, digit_bits: int = 32) -> np.ndarray:
         """Recombine digit planes mod order (object math: digits may carry)."""
         self._check_digits(digit_bits)
+        self._check_window(planes.shape[0], digit_bits)
         arr = planes.numpy().view(_U64)
         total = np.zeros(arr.shape[1], dtype=object)
         for d in reversed(range(planes.shape[0])):

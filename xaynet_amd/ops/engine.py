@@ -80,14 +80,19 @@ class GpuMaskedAggregator(MaskedAggregatorBase):
             return t[0].data_ptr(), t[1].data_ptr(), t.shape[1]
         return t.data_ptr(), 0, t.shape[0]
 
-    def _planes(self, planes: torch.Tensor, n: int):
+    def _planes(self, planes: torch.Tensor, n: int, read_bits: int | None = None):
         """Digit-plane tensor -> (ptr, k): contiguous int64 [k, n] planes for
-        values of n elements; u64 orders have exactly n_digits planes."""
+        values of n elements; u64 orders have exactly n_digits planes. Planes
+        that a kernel reads back into one integer pass their digit width as
+        read_bits: their shape must lie inside the reduction window
+        (plane_window_ok)."""
         if planes.dtype != torch.int64 or planes.dim() != 2 or not planes.is_contiguous() \
                 or planes.shape[1] != n:
             raise ValueError(f"planes must be a contiguous [k, {n}] int64 tensor")
         if not self.wide and planes.shape[0] != self.n_digits:
             raise ValueError(f"u64-order planes are [{self.n_digits}, n]")
+        if read_bits is not None and 1 <= read_bits <= 63:  # other widths: _hip refuses
+            self._check_window(planes.shape[0], read_bits)
         return planes.data_ptr(), planes.shape[0]
 
     # ---------------- mask expansion (K1) ----------------
@@ -149,6 +154,7 @@ class GpuMaskedAggregator(MaskedAggregatorBase):
 
     def aggregate_pool(self, pool: torch.Tensor, n_updates: int, unit_sum: int = 0):
         """Accumulate n_updates packed rows into the digit planes."""
+        self._check_headroom(n_updates)
         _hip.aggregate_batch(
             self.acc.data_ptr(), pool.data_ptr(), pool.stride(0), n_updates, self.length,
             self.bpn, int(os.environ.get("XAYNET_K3_EPT", "0"))
@@ -183,7 +189,7 @@ class GpuMaskedAggregator(MaskedAggregatorBase):
         """Canonicalize a contiguous [k, n] plane tensor mod order (the
         inverse layout of values_to_planes)."""
         lo, hi, n = self._vals(out)
-        ptr, k = self._planes(planes, n)
+        ptr, k = self._planes(planes, n, read_bits=digit_bits)
         _hip.canonicalize(ptr, lo, hi, n, k, self.order, digit_bits)
 
     def recode_planes(self, out_planes: torch.Tensor, digit_bits: int) -> torch.Tensor:
@@ -237,7 +243,7 @@ class GpuMaskedAggregator(MaskedAggregatorBase):
         slice mask[lo:lo+n] / mask[:, lo:lo+n]. Wide orders take planes of
         digit_bits-wide digits."""
         lo, hi, n = self._vals(mask_values)
-        ptr, k = self._planes(planes, n)
+        ptr, k = self._planes(planes, n, read_bits=digit_bits)
         scalar_sum, vinfo, dt = self._unmask_scalars(mask_unit, nb_models, dtype)
         out = torch.empty(n, dtype=self._TORCH_DTYPES[dt], device=planes.device)
         if self.bmax or self.exact_integers(vinfo, dt):
