@@ -14,6 +14,11 @@ echo "== CPU suite =="
 python -m pytest tests -q -m "not gpu"
 
 echo "== sanitizers =="
+# the GPU model encoder's element functions, as a stand-alone host program
+mkdir -p build
+g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
+    -Ixaynet_amd/csrc scripts/model_codec_sanitize.cpp -o build/model_codec_sanitize
+build/model_codec_sanitize
 bash scripts/sanitize.sh
 bash scripts/tsan.sh
 

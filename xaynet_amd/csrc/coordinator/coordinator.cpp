@@ -874,10 +874,10 @@ bool Coordinator::pending_unmask(Bytes& mask_bytes, uint64_t& nb_models) {
     return true;
 }
 
-void Coordinator::supply_unmasked_model(const Bytes& model_bincode) {
+void Coordinator::supply_unmasked_model(Bytes model_bincode) {
     {
         std::lock_guard<std::mutex> l(unmask_mu_);
-        unmask_result_ = model_bincode;
+        unmask_result_ = std::move(model_bincode);
     }
     unmask_cv_.notify_all();
 }

@@ -164,8 +164,9 @@ class Coordinator {
     // true when the Unmask phase is waiting for an external unmask result;
     // returns the winning aggregated-mask wire bytes + nb_models
     bool pending_unmask(Bytes& mask_bytes, uint64_t& nb_models);
-    // supply the unmasked model (bincode Option<Model> payload = Some body)
-    void supply_unmasked_model(const Bytes& model_bincode);
+    // supply the unmasked model (bincode Option<Model> payload = Some body);
+    // taken by value and moved into place, so an rvalue is not copied again
+    void supply_unmasked_model(Bytes model_bincode);
 
     // checkpoint (bincode CoordinatorState, reference-compatible layout).
     // NOT thread-safe vs a running phase loop: call from the protocol thread

@@ -420,8 +420,25 @@ void bind_coordinator(py::module_& m) {
                  if (!c.pending_unmask(mb, nb)) return py::none();
                  return py::make_tuple(pyb(mb), nb);
              })
+        // any C-contiguous buffer (bytes, memoryview, a uint8 numpy view of
+        // pinned memory): copied once, into the coordinator's own storage
         .def("supply_unmasked_model",
-             [](Coordinator& c, py::bytes model) { c.supply_unmasked_model(frompy(model)); })
+             [](Coordinator& c, const py::buffer& model) {
+                 Py_buffer view;
+                 if (PyObject_GetBuffer(model.ptr(), &view, PyBUF_C_CONTIGUOUS) != 0)
+                     throw py::error_already_set();
+                 Bytes body;
+                 try {
+                     py::gil_scoped_release rel;
+                     const auto* p = static_cast<const uint8_t*>(view.buf);
+                     body.assign(p, p + view.len);
+                 } catch (...) {
+                     PyBuffer_Release(&view);
+                     throw;
+                 }
+                 PyBuffer_Release(&view);
+                 c.supply_unmasked_model(std::move(body));
+             })
         .def("checkpoint_state", [](Coordinator& c) { return pyb(c.checkpoint_state()); })
         .def("restore_state", [](Coordinator& c, py::bytes st) { return c.restore_state(frompy(st)); });
 }

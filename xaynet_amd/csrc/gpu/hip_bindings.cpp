@@ -430,6 +430,57 @@ PYBIND11_MODULE(_hip, m) {
         },
         py::arg("src"), py::arg("bytes"), py::arg("nontemporal"), py::arg("sink"), nogil);
 
+    // private (ops/engine.py encode_model, tests): K7, the weights at `src`
+    // (dtype 0=F32 1=F64 2=I32 3=I64) as their Option<Model> bincode body.
+    // Returns the body's length in bytes. The body is written at out + 3 (its
+    // words are then aligned) if out_bytes >= 3 + that length; a smaller
+    // buffer is left untouched, and the caller calls again with a larger one.
+    // The length is data-dependent (28..168 bytes per element), so it is read
+    // back from the device, 8 bytes, between the count and the emit: sizing
+    // `out` for the worst case instead would take 1.5x (F32) to 4x (F64) the
+    // memory of a typical body. `work` holds _model_plan(len)["work_bytes"]
+    // bytes. len == 0 launches nothing: the body is then the 9-byte head alone,
+    // which the caller has without a device.
+    m.def(
+        "_model_encode",
+        [](uintptr_t src, int dtype, uint64_t len, uintptr_t work, uintptr_t out,
+           uint64_t out_bytes) -> uint64_t {
+            if (dtype < 0 || dtype > 3) throw py::value_error("dtype must be 0..3");
+            if (len > (uint64_t(1) << 32))
+                throw py::value_error("a model has at most 2^32 weights");
+            if (len == 0) return 9;
+            py::gil_scoped_release release;
+            void* w = reinterpret_cast<void*>(src);
+            void* ws = reinterpret_cast<void*>(work);
+            check(xhip_k7_model_count(w, dtype, len, ws), "k7_model_count");
+            uint64_t words = 0;
+            check(hipMemcpy(&words, ws, sizeof words, hipMemcpyDeviceToHost), "k7 total");
+            const uint64_t body = 9 + 4 * words;
+            if (out_bytes >= 3 + body)
+                check(xhip_k7_model_emit(w, dtype, len, ws, u8p(out), out_bytes),
+                      "k7_model_emit");
+            return body;
+        },
+        py::arg("src"), py::arg("dtype"), py::arg("len"), py::arg("work"), py::arg("out"),
+        py::arg("out_bytes"));
+
+    // private: how _model_encode splits `len` weights (XhipK7Plan, kernels.h)
+    m.def(
+        "_model_plan",
+        [](uint64_t len) {
+            XhipK7Plan p;
+            xhip_k7_plan(len, &p);
+            py::dict d;
+            d["block_elems"] = p.block_elems;
+            d["blocks"] = p.blocks;
+            d["scan_levels"] = p.scan_levels;
+            d["tile_blocks"] = p.tile_blocks;
+            d["tiles"] = p.tiles;
+            d["work_bytes"] = p.work_bytes;
+            return d;
+        },
+        py::arg("len"));
+
     // [n_planes][len] digit planes minus the mask -> model weights.
     // dtype follows mask::DataType: 0=F32 1=F64 2=I32 3=I64
     // Bmax configs, and integer outputs of the other bounds, pass `offset` =

@@ -130,6 +130,31 @@ hipError_t xhip_k6_unpack(const uint8_t* in, uint64_t* out_lo, uint64_t* out_hi,
 hipError_t xhip_k6_pack(const uint64_t* in_lo, const uint64_t* in_hi, uint8_t* out, uint64_t len,
                         int bpn);
 
+// ---- K7: model weights -> Option<Model> bincode body ----
+//
+// How the encoder splits `len` weights: blocks of block_elems elements, whose
+// word totals are scanned to 64-bit bases in scan_levels levels. Up to
+// XHIP_K7_SCAN_ONE_WG blocks one workgroup scans the block totals themselves
+// (1 level, tiles == 0); more are scanned inside `tiles` tiles of tile_blocks
+// blocks first, and that workgroup scans the tile totals (2 levels).
+// work_bytes is the workspace both launchers take; all zero for len == 0 or
+// len > 2^32 (the model decoder's own limit).
+#define XHIP_K7_SCAN_ONE_WG 4096
+struct XhipK7Plan {
+    uint32_t block_elems, scan_levels, tile_blocks;
+    uint64_t blocks, tiles, work_bytes;
+};
+void xhip_k7_plan(uint64_t len, XhipK7Plan* plan);
+// Counts and scans: afterwards the first u64 of `work` (16-byte aligned,
+// work_bytes long) is the number of u32 words of all elements, and the body
+// is 9 + 4 * that many bytes. len in 1..2^32.
+hipError_t xhip_k7_model_count(const void* w, int dtype, uint64_t len, void* work);
+// Writes the body at out + 3 (so that its words are aligned dwords; out
+// 4-byte aligned) from the workspace xhip_k7_model_count left for the same
+// w, dtype and len. Nothing is stored at or past out + out_bytes.
+hipError_t xhip_k7_model_emit(const void* w, int dtype, uint64_t len, const void* work,
+                              uint8_t* out, uint64_t out_bytes);
+
 // ---- every width: u64, u128 and multi-limb orders below 2^320 ----
 //
 // The launchers the bindings call. The order travels by value as five u64

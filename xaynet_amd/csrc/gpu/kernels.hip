@@ -6,6 +6,7 @@
 //   K4 unmask finalize        <- Aggregation::unmask    (masking.rs:190-231)
 //   K5 mask+pack              <- Masker::mask           (masking.rs:358-404)
 //   K6 pack/unpack limbs      <- object/serialization/vect.rs limb codec
+//   K7 model -> bincode body  <- bincode serialisation of Model (Vec<Ratio<BigInt>>)
 //
 // Design (MI355X-first, not a port):
 //  * Masked vectors live in HBM in the WIRE format itself: a dense
@@ -35,6 +36,7 @@
 // bits) take the CPU oracle.
 #include "kernels.h"
 #include "mask_quant.h"
+#include "model_codec.h"
 #include "u192.h"
 
 #include <algorithm>
@@ -89,19 +91,19 @@ __device__ void chacha20_block_dev(const uint32_t key[8], uint64_t counter, uint
 // Hillis-Steele scan cost 16 barriers). Returns the calling thread's
 // exclusive prefix; afterwards wave_tot[w] holds wavefront w's total, so the
 // block total is their sum.
-template <int NW>
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t mine, uint32_t* wave_tot) {
+template <int NW, typename V = uint32_t>
+__device__ __forceinline__ V block_excl_scan(V mine, V* wave_tot) {
     uint32_t lane = threadIdx.x & 63;
     uint32_t wave = threadIdx.x >> 6;
-    uint32_t incl = mine;
+    V incl = mine;
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {
-        uint32_t v = __shfl_up(incl, off, 64);
+        V v = __shfl_up(incl, off, 64);
         if (int(lane) >= off) incl += v;
     }
     if (lane == 63) wave_tot[wave] = incl;
     __syncthreads();
-    uint32_t wave_base = 0;
+    V wave_base = 0;
 #pragma unroll
     for (uint32_t w = 0; w < NW; ++w) {
         if (w < wave) wave_base += wave_tot[w];
@@ -1386,6 +1388,87 @@ __global__ void k5_mask_weights_exact(
     ml_pack_bytes<L>(out + i * bpn, bpn, val);
 }
 
+// ------------------------------------------- K7: model -> bincode body
+//
+// The unmasked weights as the Option<Model> bincode body the coordinator
+// publishes (encode_option_model_* in message/bincode.cpp): u8 1, u64 n, then
+// one Ratio<BigInt> element per weight. An element is 7..42 u32 words
+// (model_codec.h), so the encoding is a compaction like K1's: count, scan,
+// scatter.
+//   k7_model_words   block b's word total (one element per thread)
+//   scan             the block totals to 64-bit word bases: XHIP_K7_SCAN_ONE_WG
+//                    totals or fewer by k7_scan_bases alone; more by
+//                    k1_scan_blocks (u32 prefixes inside tiles of 1024 blocks,
+//                    at most 1024 * 256 * 42 words) and k7_scan_bases over the
+//                    tile totals. Bases are u64: a 1B-parameter body is past
+//                    2^32 bytes.
+//   k7_model_emit    recounts its block (cheaper than storing and reloading a
+//                    prefix per element) and writes each element's words at
+//                    block base + in-block prefix
+// The body sits at byte 3 of the output buffer: its 9-byte head then ends on
+// a dword boundary and every element word is a naturally aligned dword store.
+// A wave writes one contiguous span (about 2 KiB for f32 weights).
+#define K7_BLOCK 256
+#define K7_SCAN_THREADS 1024
+
+template <typename T>
+__global__ void __launch_bounds__(K7_BLOCK) k7_model_words(
+    const T* __restrict__ w, uint64_t len, uint32_t* __restrict__ blk_tot) {
+    __shared__ uint32_t wave_tot[K7_BLOCK / WAVE];
+    const uint64_t i = uint64_t(blockIdx.x) * K7_BLOCK + threadIdx.x;
+    block_excl_scan<K7_BLOCK / WAVE>(i < len ? mc_words(mc_decompose(w[i])) : 0u, wave_tot);
+    if (threadIdx.x == 0)
+        blk_tot[blockIdx.x] = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
+}
+
+// One workgroup: exclusive u64 prefixes of n u32 totals, K7_SCAN_THREADS at a
+// time with a running carry, and the grand total.
+__global__ void __launch_bounds__(K7_SCAN_THREADS) k7_scan_bases(
+    const uint32_t* __restrict__ tot, uint32_t n, uint64_t* __restrict__ bases,
+    uint64_t* __restrict__ total) {
+    __shared__ uint64_t wave_tot[K7_SCAN_THREADS / WAVE];
+    uint64_t carry = 0;
+    for (uint32_t c = 0; c < n; c += K7_SCAN_THREADS) {
+        const uint32_t idx = c + threadIdx.x;
+        const uint64_t prefix =
+            block_excl_scan<K7_SCAN_THREADS / WAVE>(uint64_t(idx < n ? tot[idx] : 0u), wave_tot);
+        if (idx < n) bases[idx] = carry + prefix;
+#pragma unroll
+        for (int j = 0; j < K7_SCAN_THREADS / WAVE; ++j) carry += wave_tot[j];
+        __syncthreads();  // wave_tot is read; the next chunk's scan overwrites it
+    }
+    if (threadIdx.x == 0) *total = carry;
+}
+
+// in_tile is null where k7_scan_bases ran over the block totals themselves
+// (shift 0); else bases holds one entry per tile of 2^shift blocks. out_words
+// is the buffer's capacity in words, head included.
+template <typename T>
+__global__ void __launch_bounds__(K7_BLOCK) k7_model_emit(
+    const T* __restrict__ w, uint64_t len, const uint64_t* __restrict__ bases,
+    const uint32_t* __restrict__ in_tile, int shift, uint32_t* __restrict__ out,
+    uint64_t out_words) {
+    __shared__ uint32_t wave_tot[K7_BLOCK / WAVE];
+    const uint64_t i = uint64_t(blockIdx.x) * K7_BLOCK + threadIdx.x;
+    mc_value v = mc_value{0, 0, false};
+    uint32_t nw = 0;
+    if (i < len) {
+        v = mc_decompose(w[i]);
+        nw = mc_words(v);
+    }
+    const uint32_t prefix = block_excl_scan<K7_BLOCK / WAVE>(nw, wave_tot);
+    if (i == 0) {
+        // the head, u8 1 | u64 len, in bytes 3..11
+        reinterpret_cast<uint8_t*>(out)[3] = 1;
+        out[1] = uint32_t(len);
+        out[2] = uint32_t(len >> 32);
+    }
+    const uint64_t at = 3 + bases[blockIdx.x >> shift] +
+                        (in_tile ? in_tile[blockIdx.x] : 0u) + prefix;
+    // the launcher sized `out` from the same counts; never write past it
+    if (i < len && at + nw <= out_words) mc_write(v, out + at);
+}
+
 // ===================================================================
 // Host-side launchers (C ABI declared in kernels.h, consumed by
 // hip_bindings.cpp). All launches go to the null stream, which serializes
@@ -1820,6 +1903,91 @@ hipError_t xhip_k6_pack(const uint64_t* in_lo, const uint64_t* in_hi, uint8_t* o
                         int bpn) {
     if (!in_hi) return launch_1d(k6_pack_u64, len, in_lo, out, len, bpn);
     return launch_1d(k6_pack_u128, len, in_lo, in_hi, out, len, bpn);
+}
+
+// ---- K7: count -> scan -> emit ----
+
+#define K7_TILE_SHIFT 10  // one k1_scan_blocks workgroup scans 1024 totals
+#define K7_TILE_BLOCKS (1u << K7_TILE_SHIFT)
+
+// The workspace: the total, the u64 bases (one per block, or per tile), then
+// the u32 block totals on a 16-byte boundary (k1_scan_blocks loads them four
+// at a time) and the u32 tile totals.
+struct K7Workspace {
+    uint64_t n_bases, blk_tot, tile_tot, end;  // byte offsets but for n_bases
+};
+static K7Workspace k7_workspace(const XhipK7Plan& p) {
+    K7Workspace ws;
+    ws.n_bases = p.scan_levels == 2 ? p.tiles : p.blocks;
+    ws.blk_tot = (8 + 8 * ws.n_bases + 15) / 16 * 16;
+    ws.tile_tot = ws.blk_tot + 4 * p.blocks;
+    ws.end = ws.tile_tot + 4 * p.tiles;
+    return ws;
+}
+
+void xhip_k7_plan(uint64_t len, XhipK7Plan* plan) {
+    *plan = XhipK7Plan{};
+    if (len == 0 || len > (uint64_t(1) << 32)) return;
+    plan->block_elems = K7_BLOCK;
+    plan->blocks = (len + K7_BLOCK - 1) / K7_BLOCK;
+    plan->scan_levels = plan->blocks <= XHIP_K7_SCAN_ONE_WG ? 1 : 2;
+    if (plan->scan_levels == 2) {
+        plan->tile_blocks = K7_TILE_BLOCKS;
+        plan->tiles = (plan->blocks + K7_TILE_BLOCKS - 1) / K7_TILE_BLOCKS;
+    }
+    plan->work_bytes = k7_workspace(*plan).end;
+}
+
+hipError_t xhip_k7_model_count(const void* w, int dtype, uint64_t len, void* work) {
+    XhipK7Plan p;
+    xhip_k7_plan(len, &p);
+    if (p.blocks == 0 || !w || !work || reinterpret_cast<uintptr_t>(work) % 16)
+        return hipErrorInvalidValue;
+    const K7Workspace ws = k7_workspace(p);
+    uint8_t* base = static_cast<uint8_t*>(work);
+    uint64_t* total = reinterpret_cast<uint64_t*>(base);
+    uint64_t* bases = total + 1;
+    uint32_t* blk_tot = reinterpret_cast<uint32_t*>(base + ws.blk_tot);
+    uint32_t* tile_tot = reinterpret_cast<uint32_t*>(base + ws.tile_tot);
+    const uint32_t blocks = uint32_t(p.blocks), tiles = uint32_t(p.tiles);
+    hipError_t e = dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(k7_model_words<T>, dim3(blocks), dim3(K7_BLOCK), 0, 0,
+                           static_cast<const T*>(w), len, blk_tot);
+        return hipGetLastError();
+    });
+    if (e != hipSuccess) return e;
+    if (p.scan_levels == 1) {
+        hipLaunchKernelGGL(k7_scan_bases, dim3(1), dim3(K7_SCAN_THREADS), 0, 0, blk_tot, blocks,
+                           bases, total);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(k1_scan_blocks, dim3(tiles), dim3(256), 0, 0, blk_tot, blocks, tile_tot);
+    hipLaunchKernelGGL(k7_scan_bases, dim3(1), dim3(K7_SCAN_THREADS), 0, 0, tile_tot, tiles,
+                       bases, total);
+    return hipGetLastError();
+}
+
+hipError_t xhip_k7_model_emit(const void* w, int dtype, uint64_t len, const void* work,
+                              uint8_t* out, uint64_t out_bytes) {
+    XhipK7Plan p;
+    xhip_k7_plan(len, &p);
+    if (p.blocks == 0 || !w || !work || !out || reinterpret_cast<uintptr_t>(out) % 4 ||
+        out_bytes < 12)  // the head alone
+        return hipErrorInvalidValue;
+    const K7Workspace ws = k7_workspace(p);
+    const uint8_t* base = static_cast<const uint8_t*>(work);
+    const uint64_t* bases = reinterpret_cast<const uint64_t*>(base) + 1;
+    const uint32_t* blk_tot = reinterpret_cast<const uint32_t*>(base + ws.blk_tot);
+    const bool tiled = p.scan_levels == 2;
+    return dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(k7_model_emit<T>, dim3(uint32_t(p.blocks)), dim3(K7_BLOCK), 0, 0,
+                           static_cast<const T*>(w), len, bases, tiled ? blk_tot : nullptr,
+                           tiled ? K7_TILE_SHIFT : 0, reinterpret_cast<uint32_t*>(out),
+                           out_bytes / 4);
+        return hipGetLastError();
+    });
 }
 
 // ---- every width: forward L <= 2, run the multi-limb kernels for L = 3..5 ----

@@ -4,7 +4,12 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <cstring>
+#include <string>
+#include <vector>
+
 #include "crypto/curve25519.h"
+#include "gpu/model_codec.h"
 #include "sdk/participant.h"
 
 namespace py = pybind11;
@@ -72,6 +77,34 @@ class PyTransportClient : public XaynetClient {
 
     py::function get_, post_;
 };
+
+// ---- model_codec_*: the GPU's model encoder (gpu/model_codec.h) on the host
+
+template <typename T>
+static std::vector<uint32_t> codec_counts(const T* v, size_t n) {
+    std::vector<uint32_t> words(n);
+    for (size_t i = 0; i < n; ++i) words[i] = mc_words(mc_decompose(v[i]));
+    return words;
+}
+
+// f(typed data, n) for a 1-D f32/f64/i32/i64 array, taken as typed
+template <typename F>
+static auto codec_dispatch(const py::array& w, F f) {
+    if (w.ndim() != 1) throw py::value_error("model must be a 1-D array");
+    const size_t n = size_t(w.shape(0));
+    const int tn = w.dtype().num();  // by type number, not identity
+    auto as = [&](auto zero) {
+        using T = decltype(zero);
+        auto a = py::array_t<T, py::array::c_style>::ensure(w);
+        if (!a) throw py::value_error("model must be a 1-D array");
+        return f(a.data(), n);
+    };
+    if (tn == py::dtype::of<float>().num()) return as(float(0));
+    if (tn == py::dtype::of<double>().num()) return as(double(0));
+    if (tn == py::dtype::of<int32_t>().num()) return as(int32_t(0));
+    if (tn == py::dtype::of<int64_t>().num()) return as(int64_t(0));
+    throw py::value_error("model dtype must be f32/f64/i32/i64");
+}
 
 void bind_sdk(py::module_& m) {
     auto s = m.def_submodule("sdk");
@@ -310,5 +343,35 @@ void bind_sdk(py::module_& m) {
             em.assemble(dst);
         }
         return holder;
+    });
+
+    // The GPU's model encoder (gpu/model_codec.h, what the K7 kernels compile)
+    // in a plain loop on the host: the Option<Model> body of a 1-D
+    // f32/f64/i32/i64 array, and the u32 words per element.
+    s.def("model_codec_encode", [](const py::array& w) -> py::bytes {
+        return codec_dispatch(w, [](const auto* v, size_t n) {
+            std::vector<uint32_t> words = codec_counts(v, n);
+            size_t total = 0;
+            for (uint32_t c : words) total += c;
+            std::string body(9 + 4 * total, '\0');
+            body[0] = 1;
+            const uint64_t n64 = n;
+            std::memcpy(&body[1], &n64, 8);  // little-endian hosts only, like the kernels
+            // elements start 1 mod 4 in the body: encode into aligned words
+            std::vector<uint32_t> buf(total);
+            size_t at = 0;
+            for (size_t i = 0; i < n; ++i) {
+                mc_write(mc_decompose(v[i]), buf.data() + at);
+                at += words[i];
+            }
+            if (total) std::memcpy(&body[9], buf.data(), 4 * total);
+            return py::bytes(body);
+        });
+    });
+    s.def("model_codec_words", [](const py::array& w) -> py::array_t<uint32_t> {
+        return codec_dispatch(w, [](const auto* v, size_t n) {
+            std::vector<uint32_t> words = codec_counts(v, n);
+            return py::array_t<uint32_t>(py::ssize_t(n), words.data());
+        });
     });
 }

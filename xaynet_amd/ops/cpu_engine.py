@@ -46,6 +46,7 @@ class CpuPlaneAggregator(MaskedAggregatorBase):
     """Digit-plane aggregation of wire-format masked updates on the CPU."""
 
     _NP_DTYPES = {0: np.float32, 1: np.float64, 2: np.int32, 3: np.int64}
+    _MODEL_DTYPES = (torch.float32, torch.float64, torch.int32, torch.int64)
 
     def __init__(self, vect_cfg, unit_cfg, length: int, device: str = "cpu",
                  sum2_budget_bytes: int = DEFAULT_SUM2_BUDGET_BYTES):
@@ -284,3 +285,13 @@ class CpuPlaneAggregator(MaskedAggregatorBase):
         return (bytes(self.vect_cfg.to_bytes()) + (limbs.numel() // self.bpn).to_bytes(4, "big")
                 + limbs.numpy().tobytes() + bytes(self.unit_cfg.to_bytes())
                 + int(unit_value).to_bytes(ubpn, "little"))
+
+    def encode_model(self, weights: torch.Tensor) -> np.ndarray:
+        """The Option<Model> bincode body of unmasked weights (a contiguous
+        1-D f32/f64/i32/i64 CPU tensor; ValueError otherwise) as a uint8
+        array: the bytes the GPU engine's encode_model returns."""
+        if not isinstance(weights, torch.Tensor) or weights.dim() != 1 \
+                or not weights.is_contiguous() or weights.device.type != "cpu" \
+                or weights.dtype not in self._MODEL_DTYPES:
+            raise ValueError("encode_model takes a contiguous 1-D f32/f64/i32/i64 CPU tensor")
+        return np.frombuffer(_core.sdk.encode_model(weights.numpy()), dtype=np.uint8)

@@ -3,8 +3,9 @@
 The C++ coordinator (AggregationPlane::Staged) validates and stages masked
 updates as MaskObject wire bytes during the Update phase; this driver drains
 them onto the MI355X, aggregates limbs in digit planes (K3), and at Unmask
-derives the final model (K6 unpack + K4 modular finalize/unmask), returning
-the bincode Option<Model> body the coordinator broadcasts and persists.
+derives the final model (K6 unpack + K4 modular finalize/unmask) and encodes
+it on the device (K7) into the bincode Option<Model> body the coordinator
+broadcasts and persists.
 
 This replaces the reference's in-RAM `Aggregation::aggregate` hot loop
 (rust/xaynet-core/src/mask/masking.rs:292-316) with the GPU engine while the
@@ -22,8 +23,6 @@ import threading
 
 import numpy as np
 import torch
-
-from xaynet_amd import _core
 
 from .engine import GpuMaskedAggregator
 
@@ -94,8 +93,9 @@ class GpuCoordinatorDriver(threading.Thread):
         t = torch.frombuffer(bytearray(mask_vect), dtype=torch.uint8).to(self.eng.device)
         mask_vals = self.eng.unpack_wire(t)
         out = self.eng.unmask(mask_vals, mask_unit, nb_models=nb_models)
-        body = _core.sdk.encode_model(out.cpu().numpy())
-        self.coordinator.supply_unmasked_model(body)
+        # K7: the body is encoded on the GPU and lands in pinned host memory;
+        # the coordinator copies that view once, into its own storage
+        self.coordinator.supply_unmasked_model(self.eng.encode_model(out))
         self.eng.reset()
         self.rounds_unmasked += 1
 

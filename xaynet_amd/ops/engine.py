@@ -61,6 +61,8 @@ class GpuMaskedAggregator(MaskedAggregatorBase):
         with torch.cuda.device(self.device):
             self._expander = _hip.MaskExpander()
         self._wire_pin = None  # cached pinned staging buffer of wire_object
+        # encode_model: cached workspace, device body and pinned staging buffer
+        self._enc_work = self._enc_dev = self._enc_pin = None
 
     # ---------------- tensor forms ----------------
 
@@ -352,3 +354,49 @@ class GpuMaskedAggregator(MaskedAggregatorBase):
         wire[off : off + 4] = bytes(self.unit_cfg.to_bytes())
         wire[off + 4 :] = int(unit_value).to_bytes(ubpn, "little")
         return bytes(wire)
+
+    # ---------------- model body (K7) ----------------
+
+    # a first guess at the body's bytes per weight (zero 28, a typical f32 32,
+    # a typical f64 36..40); a longer body grows the buffers and runs again
+    _ENC_GUESS = {0: 36, 1: 48, 2: 36, 3: 40}
+
+    def encode_model(self, weights: torch.Tensor) -> np.ndarray:
+        """The Option<Model> bincode body of unmasked weights, encoded on the
+        GPU (K7): byte for byte what _core.sdk.encode_model gives for the same
+        values. `weights` is a contiguous 1-D f32/f64/i32/i64 tensor on this
+        engine's device, of any length (ValueError otherwise, before any
+        launch). Returns a uint8 numpy view of a cached pinned staging buffer,
+        valid until the next call on this engine."""
+        dt = self._WEIGHT_DTYPES.get(weights.dtype) if isinstance(weights, torch.Tensor) else None
+        if dt is None or weights.dim() != 1 or not weights.is_contiguous() \
+                or weights.device != self.acc.device:
+            raise ValueError("encode_model takes a contiguous 1-D f32/f64/i32/i64 tensor on "
+                             f"{self.acc.device}")
+        n = weights.numel()
+        if n == 0:
+            return np.frombuffer(b"\x01" + bytes(8), dtype=np.uint8)
+        with torch.cuda.device(self.acc.device):
+            work = self._enc_buffer("_enc_work", _hip._model_plan(n)["work_bytes"])
+            out = self._enc_buffer("_enc_dev", 3 + 9 + n * self._ENC_GUESS[dt])
+            body = _hip._model_encode(weights.data_ptr(), dt, n, work.data_ptr(),
+                                      out.data_ptr(), out.numel())
+            if 3 + body > out.numel():  # nothing was written: grow, run again
+                out = self._enc_buffer("_enc_dev", 3 + body)
+                body = _hip._model_encode(weights.data_ptr(), dt, n, work.data_ptr(),
+                                          out.data_ptr(), out.numel())
+            if self._enc_pin is None or self._enc_pin.numel() < 3 + body:
+                self._enc_pin = torch.empty(3 + body + (3 + body) // 8, dtype=torch.uint8,
+                                            pin_memory=True)
+            pin = self._enc_pin[: 3 + body]
+            pin.copy_(out[: 3 + body])  # device to pinned host: synchronous
+        return pin.numpy()[3:]
+
+    def _enc_buffer(self, name: str, nbytes: int) -> torch.Tensor:
+        """A cached device byte buffer of at least nbytes (contents not kept)."""
+        buf = getattr(self, name)
+        if buf is None or buf.numel() < nbytes:
+            setattr(self, name, None)  # free before growing
+            buf = torch.empty(nbytes + nbytes // 8, dtype=torch.uint8, device=self.device)
+            setattr(self, name, buf)
+        return buf
