@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """Time k3_aggregate variants on MI355X: the generic kernel's EPT values, the
-LDS-staged kernels (201 / 202) and the tile-streaming kernel (401 nontemporal,
-402 default loads).
+LDS-staged kernels (201 / 202), the tile-streaming kernel (401 nontemporal,
+402 default loads) and its loader-wave form (411 nontemporal, 412 default).
 
 Usage: python scripts/k3_sweep.py [--length 25000000] [--pool 300] [--bpn 7]
-           [--epts 0,4,401,402] [--ceiling] [--check]
+           [--epts 0,4,401,402,411,412] [--ceiling] [--check]
 Prints ms/dispatch and effective read TB/s per variant. --ceiling first times a
 trivial coalesced 16-byte-per-lane read of the same pool, with default and
 nontemporal loads: the rate K3 is held against. --check compares every
@@ -76,7 +76,7 @@ def main():
     ap.add_argument("--length", type=int, default=25_000_000)
     ap.add_argument("--pool", type=int, default=300)
     ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--epts", type=str, default="0,4,8,16,401,402")
+    ap.add_argument("--epts", type=str, default="0,4,8,16,401,402,411,412")
     ap.add_argument("--bpn", type=int, default=7, choices=K3_BPNS)
     ap.add_argument("--ceiling", action="store_true",
                     help="time a plain coalesced read of the pool first")

@@ -421,6 +421,24 @@ PYBIND11_MODULE(_hip, m) {
         },
         py::arg("len"), py::arg("bpn"), py::arg("stride"));
 
+    // private (tests): what the loader-wave K3 kernel (ept 411 / 412) launches
+    m.def(
+        "_k3_loader_plan",
+        [](uint64_t len, int bpn, uint64_t stride) {
+            XhipK3LoaderPlan p;
+            xhip_k3_loader_plan(len, bpn, stride, &p);
+            py::dict d;
+            d["consumers"] = p.consumers;
+            d["depth"] = p.depth;
+            d["tile_blocks"] = p.tile_blocks;
+            d["has_remainder"] = bool(p.has_remainder);
+            d["n_tiles"] = p.n_tiles;
+            d["rem_start"] = p.rem_start;
+            d["max_byte"] = p.max_byte;
+            return d;
+        },
+        py::arg("len"), py::arg("bpn"), py::arg("stride"));
+
     m.def(
         "_read_ceiling",
         [](uintptr_t src, uint64_t bytes, bool nontemporal, uintptr_t sink) {

@@ -82,6 +82,20 @@ struct XhipK3TilePlan {
 };
 void xhip_k3_tile_plan(uint64_t len, int bpn, uint64_t stride, XhipK3TilePlan* plan);
 
+// What the loader-wave K3 kernel (ept 411 / 412) launches for the same row:
+// it takes n_tiles, rem_start and max_byte from the tile plan above and runs
+// tile_blocks workgroups of one loader wave and `consumers` consumer waves
+// over `consumers` adjacent tiles each, through a ring of `depth` LDS slots,
+// plus one remainder block if has_remainder; n_tiles, rem_start and max_byte
+// repeat the tile plan's. All zero (and -1) when the tile plan has no tile or
+// bpn has no loader kernel: the generic kernel runs then.
+struct XhipK3LoaderPlan {
+    uint32_t consumers, depth, tile_blocks, has_remainder;
+    uint64_t n_tiles, rem_start;
+    int64_t max_byte;
+};
+void xhip_k3_loader_plan(uint64_t len, int bpn, uint64_t stride, XhipK3LoaderPlan* plan);
+
 // Read-only bandwidth probe (scripts/k3_sweep.py --ceiling): reads `bytes`
 // (a multiple of 16, 16B-aligned) with coalesced 16-byte loads, default or
 // nontemporal; sink is one device word that is practically never written.

@@ -653,6 +653,184 @@ __global__ __launch_bounds__(WAVES * 64) void k3_aggregate_tile(
         for (int k = 0; k < T; ++k) acc[uint64_t(d) * len + e0 + 64 * k] += racc[k][d];
 }
 
+// K3 loader-wave variant of the tile kernel: the same tiles, the same consume
+// arithmetic and the same flush, but the LDS-DMA loads of a block all come
+// from one wave. A block is 1 + CONS waves over a group of CONS adjacent
+// tiles. Wave 0, the loader, holds no accumulators and reads no LDS: for every
+// row it issues the PB = CONS * PIECES loads of the group (CONS * TILE_BYTES
+// contiguous bytes) into one of D ring slots. Waves 1..CONS are consumers;
+// consumer c owns tile group * CONS + c - 1 and reads its part of the slot.
+// One raw barrier per row orders both directions: the loader arrives at B_k
+// after a counted vmcnt has retired row k, so the consumers read slot k mod D
+// after B_k; the consumers arrive at B_k after lgkmcnt(0) has retired their
+// reads of row k-1, so the loader refills slot (k-1) mod D after B_k. The
+// barrier is the raw s_barrier: __syncthreads() would drain vmcnt(0).
+// Every wave of a tile block executes exactly n_updates barriers: a consumer
+// whose tile is >= n_tiles (last group) attends them all and only skips the
+// reads and the flush, and the loader fetches such a tile's pieces from the
+// last full tile instead (read twice, consumed by nobody), so that its vmcnt
+// counts stay compile-time constants and no byte past the last full tile is
+// read. The remainder block (block 0 when rem_start < len) returns as a whole
+// before any barrier.
+template <int BPN, int T, int D, int CONS, int AUX>
+__global__ __launch_bounds__((1 + CONS) * 64) void k3_aggregate_loader(
+    uint64_t* __restrict__ acc, const uint8_t* __restrict__ updates, uint64_t stride,
+    uint32_t n_updates, uint64_t len, uint32_t n_tiles) {
+    constexpr int NDIG = (BPN + 3) / 4;
+    constexpr int NW = (BPN + 6) / 4;  // words an element can straddle
+    constexpr int NWAVES = 1 + CONS;
+    constexpr int TILE_BYTES = 64 * T * BPN;
+    constexpr int PIECES = TILE_BYTES / 1024;
+    constexpr int PB = CONS * PIECES;  // loads per row, all from the loader
+    // +4 words: the word after an element's last may be read (and masked off)
+    constexpr int SLOT_WORDS = TILE_BYTES / 4 + 4;
+    static_assert(TILE_BYTES % 1024 == 0, "a tile is whole 1-KiB pieces");
+    static_assert(D >= 2 && PB * (D - 2) <= 63, "vmcnt is a 6-bit count");
+    static_assert(AUX == 0 || AUX == 2, "default or nontemporal");
+    __shared__ __attribute__((aligned(16))) uint32_t ring[D * CONS * SLOT_WORDS];
+
+    const uint64_t rem_start = uint64_t(n_tiles) * (64 * T);
+    const bool has_rem = rem_start < len;  // then block 0 is the remainder block
+    if (has_rem && blockIdx.x == 0) {
+        // as in k3_aggregate_tile; the whole block leaves before any barrier
+        constexpr int KR = (T + NWAVES - 1) / NWAVES;
+        uint64_t rr[KR][NDIG];
+#pragma unroll
+        for (int k = 0; k < KR; ++k)
+#pragma unroll
+            for (int d = 0; d < NDIG; ++d) rr[k][d] = 0;
+        const uint64_t b0 = (rem_start + threadIdx.x) * BPN;  // + k*64*NWAVES*BPN: same shift
+        const uint32_t sh = uint32_t(b0) & 3;
+        for (uint32_t u = 0; u < n_updates; ++u) {
+            const uint32_t* r =
+                reinterpret_cast<const uint32_t*>(updates + uint64_t(u) * stride) + (b0 >> 2);
+#pragma unroll
+            for (int k = 0; k < KR; ++k) {
+                if (rem_start + threadIdx.x + k * (64 * NWAVES) >= len) continue;
+                uint32_t w[NW];
+#pragma unroll
+                for (int j = 0; j < NW; ++j) w[j] = r[k * (16 * NWAVES * BPN) + j];
+#pragma unroll
+                for (int d = 0; d < NDIG; ++d) {
+                    const int nb = (BPN - 4 * d) >= 4 ? 4 : (BPN - 4 * d);
+                    uint32_t val =
+                        __builtin_amdgcn_alignbyte(d + 1 < NW ? w[d + 1] : 0u, w[d], sh);
+                    if (nb < 4) val &= (1u << (8 * nb)) - 1;
+                    rr[k][d] += uint64_t(val);
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < KR; ++k) {
+            const uint64_t e = rem_start + threadIdx.x + k * (64 * NWAVES);
+            if (e >= len) continue;
+#pragma unroll
+            for (int d = 0; d < NDIG; ++d) acc[uint64_t(d) * len + e] += rr[k][d];
+        }
+        return;
+    }
+
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t tile0 = (blockIdx.x - uint32_t(has_rem)) * CONS;  // < n_tiles
+    auto next = [](uint32_t slot) { return slot + 1 == D ? 0u : slot + 1; };
+
+    if (wave == 0) {
+        // ---- loader ----
+        const uint8_t* src[CONS];
+#pragma unroll
+        for (int c = 0; c < CONS; ++c) {
+            const uint32_t t = tile0 + c < n_tiles ? tile0 + c : n_tiles - 1;
+            src[c] = updates + uint64_t(t) * TILE_BYTES + lane * 16;
+        }
+        auto issue = [&](uint32_t u, uint32_t slot) {
+            uint32_t* l = ring + slot * (CONS * SLOT_WORDS);
+#pragma unroll
+            for (int c = 0; c < CONS; ++c) {
+                const uint8_t* g = src[c] + uint64_t(u) * stride;
+#pragma unroll
+                for (int p = 0; p < PIECES; ++p) {
+                    auto gp = (const __attribute__((address_space(1))) void*)(g + p * 1024);
+                    auto lp =
+                        (__attribute__((address_space(3))) void*)(l + c * SLOT_WORDS + p * 256);
+                    // the policy must be a literal constant
+                    if constexpr (AUX == 0)
+                        __builtin_amdgcn_global_load_lds(gp, lp, 16, 0, 0);
+                    else
+                        __builtin_amdgcn_global_load_lds(gp, lp, 16, 0, 2);
+                }
+            }
+        };
+        uint32_t wslot = 0, k = 0;
+        for (; k < n_updates && k < D - 1; ++k) {  // prologue: rows 0..D-2
+            issue(k, wslot);
+            wslot = next(wslot);
+        }
+        for (k = 0; k + (D - 1) < n_updates; ++k) {
+            // rows k+1..k+D-2 may stay in flight; row k has landed
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PB * (D - 2)) : "memory");
+            __builtin_amdgcn_s_barrier();  // B_k
+            asm volatile("" ::: "memory");
+            issue(k + (D - 1), wslot);  // slot (k-1) mod D, read before B_k
+            wslot = next(wslot);
+        }
+        for (; k < n_updates; ++k) {  // drain: nothing left to issue
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();  // B_k
+        }
+        return;
+    }
+
+    // ---- consumers ----
+    const uint32_t c = wave - 1;
+    const uint32_t tile = tile0 + c;
+    const bool live = tile < n_tiles;  // wave-uniform
+    // element l + 64k starts at byte l*BPN + 64k*BPN of the tile: the shift
+    // inside its first word is the same for every k
+    const uint32_t rword = (lane * BPN) >> 2, rsh = (lane * BPN) & 3;
+    const uint32_t* const cring = ring + c * SLOT_WORDS + rword;
+
+    uint64_t racc[T][NDIG];
+#pragma unroll
+    for (int k = 0; k < T; ++k)
+#pragma unroll
+        for (int d = 0; d < NDIG; ++d) racc[k][d] = 0;
+
+    auto consume = [&](uint32_t slot) {
+        const uint32_t* r = cring + slot * (CONS * SLOT_WORDS);
+#pragma unroll
+        for (int k = 0; k < T; ++k) {
+            uint32_t w[NW];
+#pragma unroll
+            for (int j = 0; j < NW; ++j) w[j] = r[k * 16 * BPN + j];
+#pragma unroll
+            for (int d = 0; d < NDIG; ++d) {
+                const int nb = (BPN - 4 * d) >= 4 ? 4 : (BPN - 4 * d);
+                uint32_t val = __builtin_amdgcn_alignbyte(d + 1 < NW ? w[d + 1] : 0u, w[d], rsh);
+                if (nb < 4) val &= (1u << (8 * nb)) - 1;
+                racc[k][d] += uint64_t(val);
+            }
+        }
+    };
+
+    uint32_t rslot = 0;
+    for (uint32_t k = 0; k < n_updates; ++k) {
+        __builtin_amdgcn_s_barrier();  // B_k: row k is in slot k mod D
+        asm volatile("" ::: "memory");
+        if (live) consume(rslot);
+        rslot = next(rslot);
+        // this slot's reads retire before B_{k+1} lets the loader refill it
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    }
+    if (!live) return;
+
+    const uint64_t e0 = uint64_t(tile) * (64 * T) + lane;
+#pragma unroll
+    for (int d = 0; d < NDIG; ++d)
+#pragma unroll
+        for (int k = 0; k < T; ++k) acc[uint64_t(d) * len + e0 + 64 * k] += racc[k][d];
+}
+
 // Read-only ceiling probe for K3 sweeps: every lane reads 16 bytes per load,
 // a wave 1 KiB contiguous, a block 32 KiB; the XOR of the words keeps the
 // loads alive (the store practically never happens).
@@ -1600,7 +1778,9 @@ hipError_t xhip_k1_expand_batch(const uint32_t* keys_dev, const uint64_t* start_
 // The tile kernel's shape per bytes-per-number: X(BPN, T, D, WAVES). T is the
 // smallest value >= 4 with T*BPN % 16 == 0 (whole 1-KiB pieces per tile); D
 // and WAVES are the measured choice (profiles/r10_k3_tile.md). A bpn without
-// a line has no tile kernel.
+// a line has no tile kernel. It is the default of no bpn any more: bpn 7 runs
+// the loader-wave kernel below (profiles/r12_k3_loader.md), the others the
+// generic kernel; codes 401 / 402 still select it.
 #define K3_TILE_CONFIGS(X)                                                                      \
     X(3, 16, 3, 4)                                                                              \
     X(7, 16, 3, 4)                                                                              \
@@ -1626,13 +1806,44 @@ void xhip_k3_tile_plan(uint64_t len, int bpn, uint64_t stride, XhipK3TilePlan* p
     if (plan->n_tiles) plan->max_byte = int64_t(plan->rem_start * uint64_t(bpn)) - 1;
 }
 
+// The loader-wave kernel's shape per bytes-per-number: X(BPN, T, D, CONS), T
+// as above. One wave tracks at most 64 loads, so CONS * pieces * (D - 2) <= 63:
+// bpn 18 and 40 have no loader kernel. bpn 7 is the measured choice (eight
+// tiles, 56 KiB contiguous per row and block, two slots:
+// profiles/r12_k3_loader.md); bpn 3 and 10 have no benchmark and keep the tile
+// kernel's depth and tiles per block.
+#define K3_LOADER_CONFIGS(X)                                                                    \
+    X(3, 16, 3, 4)                                                                              \
+    X(7, 16, 2, 8)                                                                              \
+    X(10, 8, 3, 4)
+
+void xhip_k3_loader_plan(uint64_t len, int bpn, uint64_t stride, XhipK3LoaderPlan* plan) {
+    *plan = XhipK3LoaderPlan{0, 0, 0, 0, 0, 0, -1};
+    uint32_t d = 0, cons = 0;
+#define K3_LOADER_ROW(BPN, T, D, CONS)                                                          \
+    if (bpn == BPN) d = D, cons = CONS;
+    K3_LOADER_CONFIGS(K3_LOADER_ROW)
+#undef K3_LOADER_ROW
+    XhipK3TilePlan tiles;
+    xhip_k3_tile_plan(len, bpn, stride, &tiles);
+    if (cons == 0 || tiles.n_tiles == 0) return;
+    plan->consumers = cons;
+    plan->depth = d;
+    plan->tile_blocks = ceil_div_u32(tiles.n_tiles, cons);
+    plan->has_remainder = tiles.rem_start < len ? 1 : 0;
+    plan->n_tiles = tiles.n_tiles;
+    plan->rem_start = tiles.rem_start;
+    plan->max_byte = tiles.max_byte;
+}
+
 hipError_t xhip_k3_aggregate(uint64_t* acc, const uint8_t* updates, uint64_t stride,
                              uint32_t n_updates, uint64_t len, int bpn, int ept) {
     uint32_t threads = 256;
-    // ept<=0 is the measured default: the tile kernel with nontemporal loads
-    // where it beat the generic kernel in the benchmark, which is bpn 7 only
-    // (profiles/r10_k3_tile.md)
-    if (ept <= 0 && bpn == 7) ept = 401;
+    // ept<=0 is the measured default. bpn 7: the loader-wave kernel with
+    // nontemporal loads, which beat the tile kernel (401) in the benchmark
+    // (profiles/r12_k3_loader.md) as that had beaten the generic kernel
+    // (profiles/r10_k3_tile.md). Every other bpn: the generic kernel.
+    if (ept <= 0 && bpn == 7) ept = 411;
     // ept=401/402: tile-streaming kernel (nontemporal / default loads) where
     // the row has a full tile; needs 16B-aligned rows
     if (ept == 401 || ept == 402) {
@@ -1659,6 +1870,31 @@ hipError_t xhip_k3_aggregate(uint64_t* acc, const uint8_t* updates, uint64_t str
 #undef K3_TILE_CASE
         }
         ept = 0;  // no full tile, no tile kernel or misaligned rows: generic kernel
+    }
+    // ept=411/412: the loader-wave form of the tile kernel (nontemporal /
+    // default loads), same fall-backs
+    if (ept == 411 || ept == 412) {
+        XhipK3LoaderPlan lp;
+        xhip_k3_loader_plan(len, bpn, stride, &lp);
+        if (lp.tile_blocks && reinterpret_cast<uintptr_t>(updates) % 16 == 0) {
+#define K3_LOADER_CASE(BPN, T, D, CONS)                                                         \
+    case BPN: {                                                                                 \
+        dim3 grid(lp.tile_blocks + lp.has_remainder), block((1 + CONS) * 64);                   \
+        if (ept == 411)                                                                         \
+            hipLaunchKernelGGL((k3_aggregate_loader<BPN, T, D, CONS, 2>), grid, block, 0, 0,    \
+                               acc, updates, stride, n_updates, len, uint32_t(lp.n_tiles));     \
+        else                                                                                    \
+            hipLaunchKernelGGL((k3_aggregate_loader<BPN, T, D, CONS, 0>), grid, block, 0, 0,    \
+                               acc, updates, stride, n_updates, len, uint32_t(lp.n_tiles));     \
+        return hipGetLastError();                                                               \
+    }
+            switch (bpn) {
+                K3_LOADER_CONFIGS(K3_LOADER_CASE)
+                default:;
+            }
+#undef K3_LOADER_CASE
+        }
+        ept = 0;  // no full tile, no loader kernel or misaligned rows: generic kernel
     }
 #define K3_LAUNCH(BPN, EPT)                                                                     \
     {                                                                                           \
