@@ -19,6 +19,10 @@ mkdir -p build
 g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
     -Ixaynet_amd/csrc scripts/model_codec_sanitize.cpp -o build/model_codec_sanitize
 build/model_codec_sanitize
+# and the decoder's (mc_span / mc_read) over valid, truncated and corrupted words
+g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
+    -Ixaynet_amd/csrc scripts/model_decode_sanitize.cpp -o build/model_decode_sanitize
+build/model_decode_sanitize
 bash scripts/sanitize.sh
 bash scripts/tsan.sh
 

@@ -499,6 +499,50 @@ PYBIND11_MODULE(_hip, m) {
         },
         py::arg("len"));
 
+    // private (ops/engine.py decode_model, tests): K7d, the Option<Model>
+    // body of `nbytes` bytes at device address `body` (3 bytes past a 4-byte
+    // boundary of its buffer, where _model_encode leaves one) into `len`
+    // weights of dtype 0..3 at `out`. Returns 0 for "decoded" and non-zero for
+    // "rejected": the body is not head 01, u64 len, len canonical elements of
+    // the dtype and nothing after; `out` is then unspecified. `work` holds
+    // _model_decode_plan((nbytes - 9) / 4, tile_blocks)["work_bytes"] bytes.
+    // One status word is read back after the last kernel.
+    m.def(
+        "_model_decode",
+        [](uintptr_t body, uint64_t nbytes, int dtype, uint64_t len, uintptr_t work,
+           uintptr_t out, uint32_t tile_blocks) -> uint32_t {
+            if (dtype < 0 || dtype > 3) throw py::value_error("dtype must be 0..3");
+            if (tile_blocks > XHIP_K7D_TILE_BLOCKS)
+                throw py::value_error("tile_blocks is at most " +
+                                      std::to_string(XHIP_K7D_TILE_BLOCKS));
+            py::gil_scoped_release release;
+            uint32_t rejected = 1;
+            check(xhip_k7d_decode(reinterpret_cast<const void*>(body), nbytes, dtype, len,
+                                  reinterpret_cast<void*>(work), reinterpret_cast<void*>(out),
+                                  tile_blocks, &rejected),
+                  "k7d_decode");
+            return rejected;
+        },
+        py::arg("body"), py::arg("nbytes"), py::arg("dtype"), py::arg("len"), py::arg("work"),
+        py::arg("out"), py::arg("tile_blocks") = 0);
+
+    // private: how _model_decode splits `words` element words (XhipK7dPlan)
+    m.def(
+        "_model_decode_plan",
+        [](uint64_t words, uint32_t tile_blocks) {
+            XhipK7dPlan p;
+            xhip_k7d_plan(words, tile_blocks, &p);
+            py::dict d;
+            d["block_words"] = p.block_words;
+            d["blocks"] = p.blocks;
+            d["tile_blocks"] = p.tile_blocks;
+            d["tiles"] = p.tiles;
+            d["levels"] = p.levels;
+            d["work_bytes"] = p.work_bytes;
+            return d;
+        },
+        py::arg("words"), py::arg("tile_blocks") = 0);
+
     // [n_planes][len] digit planes minus the mask -> model weights.
     // dtype follows mask::DataType: 0=F32 1=F64 2=I32 3=I64
     // Bmax configs, and integer outputs of the other bounds, pass `offset` =

@@ -169,6 +169,34 @@ hipError_t xhip_k7_model_count(const void* w, int dtype, uint64_t len, void* wor
 hipError_t xhip_k7_model_emit(const void* w, int dtype, uint64_t len, const void* work,
                               uint8_t* out, uint64_t out_bytes);
 
+// ---- K7d: Option<Model> bincode body -> model weights ----
+//
+// How the decoder splits a body of `words` element words (the body's bytes
+// minus its 9-byte head, over 4): blocks of block_words words, whose 42-entry
+// boundary maps are composed inside `tiles` tiles of tile_blocks blocks and
+// then across the tiles (levels 2), or in the one tile alone (levels 1).
+// tile_blocks 0 asks for the default, XHIP_K7D_TILE_BLOCKS, which is also the
+// most a tile takes; a smaller one makes small bodies run both levels. All
+// zero for a tile_blocks above that or more words than 2^32 elements have.
+#define XHIP_K7D_TILE_BLOCKS 256
+struct XhipK7dPlan {
+    uint32_t block_words, tile_blocks, levels;
+    uint64_t blocks, tiles, work_bytes;
+};
+void xhip_k7d_plan(uint64_t words, uint32_t tile_blocks, XhipK7dPlan* plan);
+// Decodes the nbytes-long body at `body` (device memory, 3 bytes past a
+// 4-byte boundary inside its buffer, as K7 places it) into n weights of
+// `dtype` at `out`. `work` is 16-byte aligned and work_bytes long. *rejected
+// is 0 exactly when the body is head 01, u64 n, n canonical elements of the
+// dtype and nothing after; otherwise non-zero, and `out` is unspecified.
+// A length that is not 9 + 4 * words with 7n <= words <= 42n is refused before
+// any launch; the rest, the head included, is one status word read back after
+// the last kernel (the caller with the bytes on the host checks the head
+// there too). No word at or
+// past body + nbytes is read.
+hipError_t xhip_k7d_decode(const void* body, uint64_t nbytes, int dtype, uint64_t n, void* work,
+                           void* out, uint32_t tile_blocks, uint32_t* rejected);
+
 // ---- every width: u64, u128 and multi-limb orders below 2^320 ----
 //
 // The launchers the bindings call. The order travels by value as five u64

@@ -1647,6 +1647,209 @@ __global__ void __launch_bounds__(K7_BLOCK) k7_model_emit(
     if (i < len && at + nw <= out_words) mc_write(v, out + at);
 }
 
+// ------------------------------------------- K7d: bincode body -> model
+//
+// The inverse of K7: the Option<Model> body back to weights, accepted only
+// where it is exactly what K7 writes (mc_span / mc_read, model_codec.h).
+// Element boundaries depend on the data, so count/scan/emit does not apply
+// directly: where block b's first element starts is known only after every
+// block before it. But an element that starts in one block of K7D_BW words
+// ends at most 41 words into the next, so a block has only 42 possible entry
+// offsets, and boundary discovery is a scan over 42-entry maps:
+//   k7d_block_maps  per block and entry offset e in 0..41: follow
+//                   next(i) = i + mc_span(i) from e to the first position at
+//                   or past the block's end -> (exit offset, elements started,
+//                   valid), 42 lanes walking the spans in LDS
+//   k7d_tile_maps   the same map for a tile of tile_blocks blocks, composed
+//                   from its blocks' maps in LDS
+//   k7d_walk_tiles  one workgroup composes the tile maps in order from entry
+//                   0: each tile's true entry offset and 64-bit element base
+//   k7d_replay      per tile, from its known entry: each block's true entry
+//                   and element base; the last tile checks the count against n
+//   k7d_emit        a block lists its element starts from its entry, then
+//                   thread j decodes element j to out[base + j]
+// One tile needs neither k7d_tile_maps nor k7d_walk_tiles. A map entry is one
+// u32: exit offset (6 bits) | valid << 6 | elements << 7. Any defect (a span
+// of 0 on a chain, a chain that does not end exactly on the last word, a wrong
+// head or count, a non-canonical element) sets the status word; nothing reads
+// a word at or past the body's end, and every chain loop is bounded by
+// K7D_MAX_STEPS. The body sits at byte 3 of its buffer, as K7 leaves it.
+#define K7D_BW 2048
+#define K7D_THREADS 256
+#define K7D_ENTRIES MC_MAX_WORDS
+#define K7D_HALO (MC_MAX_WORDS - 1)
+#define K7D_MAX_STEPS (K7D_BW / 7 + 1)
+#define K7D_TILE_MAX 256  // maps of one tile in LDS: 256 * 42 * 4 bytes
+
+__device__ __forceinline__ uint32_t k7d_pack(uint32_t exit, bool valid, uint32_t count) {
+    return valid ? (exit | 64u | (count << 7)) : 0u;
+}
+
+// The block's words plus halo, clipped to the body's W words, and the span of
+// every position of the block. Returns the block's own word count.
+__device__ __forceinline__ uint32_t k7d_load_block(const uint32_t* __restrict__ words, uint64_t W,
+                                                   uint32_t* lds_w, uint8_t* lds_span) {
+    const uint64_t start = uint64_t(blockIdx.x) * K7D_BW;
+    const uint64_t left = W - start;
+    const uint32_t have = left < K7D_BW + K7D_HALO ? uint32_t(left) : K7D_BW + K7D_HALO;
+    const uint32_t bw = have < K7D_BW ? have : K7D_BW;
+    for (uint32_t i = threadIdx.x; i < have; i += K7D_THREADS) lds_w[i] = words[start + i];
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < bw; i += K7D_THREADS)
+        lds_span[i] = uint8_t(mc_span(lds_w + i, have - i));
+    __syncthreads();
+    return bw;
+}
+
+__global__ void __launch_bounds__(K7D_THREADS) k7d_block_maps(
+    const uint32_t* __restrict__ buf, uint64_t W, uint64_t n, uint32_t* __restrict__ maps,
+    uint32_t* __restrict__ status) {
+    __shared__ uint32_t lds_w[K7D_BW + K7D_HALO];
+    __shared__ uint8_t lds_span[K7D_BW];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        // the head, u8 1 | u64 n, in bytes 3..11
+        if ((buf[0] >> 24) != 1u || buf[1] != uint32_t(n) || buf[2] != uint32_t(n >> 32))
+            *status = 1;
+    }
+    const uint32_t bw = k7d_load_block(buf + 3, W, lds_w, lds_span);
+    const bool last = uint64_t(blockIdx.x) * K7D_BW + bw == W;
+    if (threadIdx.x < K7D_ENTRIES) {
+        uint32_t pos = threadIdx.x, count = 0;
+        bool valid = pos <= bw;
+        for (uint32_t step = 0; valid && pos < bw && step < K7D_MAX_STEPS; ++step) {
+            const uint32_t s = lds_span[pos];
+            if (s == 0) {
+                valid = false;
+            } else {
+                pos += s;
+                ++count;
+            }
+        }
+        // the last block's chain lands exactly on the body's end
+        if (pos < bw || (last && pos != bw)) valid = false;
+        maps[uint64_t(blockIdx.x) * K7D_ENTRIES + threadIdx.x] =
+            k7d_pack(valid ? pos - bw : 0u, valid, count);
+    }
+}
+
+// One wave per tile: lane e composes the tile's block maps from entry e.
+__global__ void __launch_bounds__(WAVE) k7d_tile_maps(
+    const uint32_t* __restrict__ maps, uint32_t blocks, uint32_t tile_blocks,
+    uint32_t* __restrict__ tile_maps) {
+    __shared__ uint32_t m[K7D_TILE_MAX * K7D_ENTRIES];
+    const uint32_t first = blockIdx.x * tile_blocks;
+    const uint32_t nb = blocks - first < tile_blocks ? blocks - first : tile_blocks;
+    for (uint32_t i = threadIdx.x; i < nb * K7D_ENTRIES; i += WAVE)
+        m[i] = maps[uint64_t(first) * K7D_ENTRIES + i];
+    __syncthreads();
+    if (threadIdx.x < K7D_ENTRIES) {
+        uint32_t cur = threadIdx.x, count = 0;
+        bool valid = true;
+        for (uint32_t b = 0; b < nb && valid; ++b) {
+            const uint32_t e = m[b * K7D_ENTRIES + cur];
+            valid = (e & 64u) != 0;
+            count += e >> 7;
+            cur = e & 63u;
+        }
+        tile_maps[uint64_t(blockIdx.x) * K7D_ENTRIES + threadIdx.x] = k7d_pack(cur, valid, count);
+    }
+}
+
+// One workgroup: the tile maps, K7D_TILE_MAX at a time through LDS, composed
+// from entry 0. tile_entry is offset | valid << 6.
+__global__ void __launch_bounds__(K7D_THREADS) k7d_walk_tiles(
+    const uint32_t* __restrict__ tile_maps, uint32_t tiles, uint64_t* __restrict__ tile_base,
+    uint32_t* __restrict__ tile_entry) {
+    __shared__ uint32_t m[K7D_TILE_MAX * K7D_ENTRIES];
+    uint32_t cur = 0;  // thread 0's, carried across chunks
+    bool valid = true;
+    uint64_t base = 0;
+    for (uint32_t c = 0; c < tiles; c += K7D_TILE_MAX) {
+        const uint32_t nt = tiles - c < K7D_TILE_MAX ? tiles - c : K7D_TILE_MAX;
+        for (uint32_t i = threadIdx.x; i < nt * K7D_ENTRIES; i += K7D_THREADS)
+            m[i] = tile_maps[uint64_t(c) * K7D_ENTRIES + i];
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            for (uint32_t t = 0; t < nt; ++t) {
+                tile_entry[c + t] = valid ? (cur | 64u) : 0u;
+                tile_base[c + t] = base;
+                if (valid) {
+                    const uint32_t e = m[t * K7D_ENTRIES + cur];
+                    valid = (e & 64u) != 0;
+                    base += e >> 7;
+                    cur = e & 63u;
+                }
+            }
+        }
+        __syncthreads();  // m is read; the next chunk overwrites it
+    }
+}
+
+// tile_entry is null for a single tile: entry 0, base 0.
+__global__ void __launch_bounds__(K7D_THREADS) k7d_replay(
+    const uint32_t* __restrict__ maps, uint32_t blocks, uint32_t tile_blocks,
+    const uint64_t* __restrict__ tile_base, const uint32_t* __restrict__ tile_entry, uint64_t n,
+    uint64_t* __restrict__ blk_base, uint32_t* __restrict__ blk_entry,
+    uint32_t* __restrict__ status) {
+    __shared__ uint32_t m[K7D_TILE_MAX * K7D_ENTRIES];
+    const uint32_t first = blockIdx.x * tile_blocks;
+    const uint32_t nb = blocks - first < tile_blocks ? blocks - first : tile_blocks;
+    for (uint32_t i = threadIdx.x; i < nb * K7D_ENTRIES; i += K7D_THREADS)
+        m[i] = maps[uint64_t(first) * K7D_ENTRIES + i];
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const uint32_t ent = tile_entry ? tile_entry[blockIdx.x] : 64u;
+    uint32_t cur = ent & 63u;
+    bool valid = (ent & 64u) != 0;
+    uint64_t base = tile_entry ? tile_base[blockIdx.x] : 0;
+    for (uint32_t b = 0; b < nb; ++b) {
+        blk_entry[first + b] = valid ? (cur | 64u) : 0u;
+        blk_base[first + b] = base;
+        if (valid) {
+            const uint32_t e = m[b * K7D_ENTRIES + cur];
+            valid = (e & 64u) != 0;
+            base += e >> 7;
+            cur = e & 63u;
+        }
+    }
+    if (!valid || (first + nb == blocks && base != n)) *status = 1;
+}
+
+template <typename T>
+__global__ void __launch_bounds__(K7D_THREADS) k7d_emit(
+    const uint32_t* __restrict__ buf, uint64_t W, uint64_t n,
+    const uint64_t* __restrict__ blk_base, const uint32_t* __restrict__ blk_entry,
+    T* __restrict__ out, uint32_t* __restrict__ status) {
+    __shared__ uint32_t lds_w[K7D_BW + K7D_HALO];
+    __shared__ uint8_t lds_span[K7D_BW];
+    __shared__ uint16_t starts[K7D_MAX_STEPS];
+    __shared__ uint32_t n_starts;
+    const uint32_t ent = blk_entry[blockIdx.x];
+    if ((ent & 64u) == 0) return;  // a broken chain before here: status is set
+    const uint32_t bw = k7d_load_block(buf + 3, W, lds_w, lds_span);
+    if (threadIdx.x == 0) {
+        uint32_t pos = ent & 63u, c = 0;
+        while (pos < bw && c < K7D_MAX_STEPS) {
+            const uint32_t s = lds_span[pos];
+            if (s == 0) break;  // k7d_block_maps marked this chain invalid
+            starts[c++] = uint16_t(pos);
+            pos += s;
+        }
+        n_starts = c;
+    }
+    __syncthreads();
+    const uint64_t base = blk_base[blockIdx.x];
+    for (uint32_t j = threadIdx.x; j < n_starts; j += K7D_THREADS) {
+        const uint32_t p = starts[j];
+        T v;
+        // base + j < n holds wherever the count check passed
+        if (base + j < n && mc_read<T>(lds_w + p, lds_span[p], &v))
+            out[base + j] = v;
+        else
+            *status = 1;
+    }
+}
+
 // ===================================================================
 // Host-side launchers (C ABI declared in kernels.h, consumed by
 // hip_bindings.cpp). All launches go to the null stream, which serializes
@@ -2224,6 +2427,95 @@ hipError_t xhip_k7_model_emit(const void* w, int dtype, uint64_t len, const void
                            out_bytes / 4);
         return hipGetLastError();
     });
+}
+
+// ---- K7d: block maps -> resolve -> emit ----
+
+// The workspace: the status word, the u64 block and tile bases, then the u32
+// block maps, tile maps, block entries and tile entries.
+struct K7dWorkspace {
+    uint64_t blk_base, tile_base, maps, tile_maps, blk_entry, tile_entry, end;  // byte offsets
+};
+static K7dWorkspace k7d_workspace(const XhipK7dPlan& p) {
+    K7dWorkspace ws;
+    ws.blk_base = 16;
+    ws.tile_base = ws.blk_base + 8 * p.blocks;
+    ws.maps = ws.tile_base + 8 * p.tiles;
+    ws.tile_maps = ws.maps + 4 * K7D_ENTRIES * p.blocks;
+    ws.blk_entry = ws.tile_maps + 4 * K7D_ENTRIES * p.tiles;
+    ws.tile_entry = ws.blk_entry + 4 * p.blocks;
+    ws.end = ws.tile_entry + 4 * p.tiles;
+    return ws;
+}
+
+void xhip_k7d_plan(uint64_t words, uint32_t tile_blocks, XhipK7dPlan* plan) {
+    *plan = XhipK7dPlan{};
+    if (tile_blocks > K7D_TILE_MAX || words > uint64_t(MC_MAX_WORDS) << 32) return;
+    plan->block_words = K7D_BW;
+    plan->tile_blocks = tile_blocks ? tile_blocks : K7D_TILE_MAX;
+    plan->blocks = (words + K7D_BW - 1) / K7D_BW;
+    plan->tiles = (plan->blocks + plan->tile_blocks - 1) / plan->tile_blocks;
+    plan->levels = plan->tiles > 1 ? 2 : 1;
+    plan->work_bytes = k7d_workspace(*plan).end;
+}
+
+hipError_t xhip_k7d_decode(const void* body, uint64_t nbytes, int dtype, uint64_t n, void* work,
+                           void* out, uint32_t tile_blocks, uint32_t* rejected) {
+    *rejected = 1;
+    if (dtype < 0 || dtype > 3 || tile_blocks > K7D_TILE_MAX) return hipErrorInvalidValue;
+    if (nbytes < 9 || (nbytes - 9) % 4 != 0) return hipSuccess;
+    const uint64_t W = (nbytes - 9) / 4;
+    if (n > (uint64_t(1) << 32) || n > W / 7 || W > MC_MAX_WORDS * n) return hipSuccess;
+    if (!body || reinterpret_cast<uintptr_t>(body) % 4 != 3) return hipErrorInvalidValue;
+    if (n == 0) {  // the head alone: nothing to launch
+        uint8_t head[9];
+        hipError_t e = hipMemcpy(head, body, sizeof head, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return e;
+        *rejected = head[0] != 1;
+        for (int i = 1; i < 9; ++i) *rejected |= head[i] != 0;
+        return hipSuccess;
+    }
+    static const size_t elem_size[4] = {4, 8, 4, 8};
+    if (!work || reinterpret_cast<uintptr_t>(work) % 16 || !out ||
+        reinterpret_cast<uintptr_t>(out) % elem_size[dtype])
+        return hipErrorInvalidValue;
+    XhipK7dPlan p;
+    xhip_k7d_plan(W, tile_blocks, &p);
+    if (p.blocks == 0) return hipErrorInvalidValue;
+    const K7dWorkspace ws = k7d_workspace(p);
+    uint8_t* base = static_cast<uint8_t*>(work);
+    uint32_t* status = reinterpret_cast<uint32_t*>(base);
+    uint64_t* blk_base = reinterpret_cast<uint64_t*>(base + ws.blk_base);
+    uint64_t* tile_base = reinterpret_cast<uint64_t*>(base + ws.tile_base);
+    uint32_t* maps = reinterpret_cast<uint32_t*>(base + ws.maps);
+    uint32_t* tile_maps = reinterpret_cast<uint32_t*>(base + ws.tile_maps);
+    uint32_t* blk_entry = reinterpret_cast<uint32_t*>(base + ws.blk_entry);
+    uint32_t* tile_entry = reinterpret_cast<uint32_t*>(base + ws.tile_entry);
+    const uint32_t* buf =
+        reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(body) - 3);
+    const uint32_t blocks = uint32_t(p.blocks), tiles = uint32_t(p.tiles);
+
+    hipError_t e = hipMemsetAsync(status, 0, 16, 0);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k7d_block_maps, dim3(blocks), dim3(K7D_THREADS), 0, 0, buf, W, n, maps,
+                       status);
+    if (p.levels == 2) {
+        hipLaunchKernelGGL(k7d_tile_maps, dim3(tiles), dim3(WAVE), 0, 0, maps, blocks,
+                           p.tile_blocks, tile_maps);
+        hipLaunchKernelGGL(k7d_walk_tiles, dim3(1), dim3(K7D_THREADS), 0, 0, tile_maps, tiles,
+                           tile_base, tile_entry);
+    }
+    hipLaunchKernelGGL(k7d_replay, dim3(tiles), dim3(K7D_THREADS), 0, 0, maps, blocks,
+                       p.tile_blocks, tile_base, p.levels == 2 ? tile_entry : nullptr, n,
+                       blk_base, blk_entry, status);
+    e = dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(k7d_emit<T>, dim3(blocks), dim3(K7D_THREADS), 0, 0, buf, W, n,
+                           blk_base, blk_entry, static_cast<T*>(out), status);
+        return hipGetLastError();
+    });
+    if (e != hipSuccess) return e;
+    return hipMemcpy(rejected, status, sizeof *rejected, hipMemcpyDeviceToHost);
 }
 
 // ---- every width: forward L <= 2, run the multi-limb kernels for L = 3..5 ----

@@ -131,3 +131,111 @@ MC_FN void mc_write(const mc_value& v, uint32_t* out) {
     for (uint32_t i = 0; i < zeros; ++i) out[i] = 0;
     out[zeros] = uint32_t(1) << (k & 31u);
 }
+
+// ---- the inverse: words -> weight (the K7d kernels, model_codec_decode) ----
+
+// The length in words (7..MC_MAX_WORDS) of an element that would start at w,
+// from its two count fields alone, or 0: both counts' high words are zero,
+// the denominator has a digit, and the element fits MC_MAX_WORDS and the
+// `avail` words that exist. Nothing at or past w + avail is read.
+MC_FN uint32_t mc_span(const uint32_t* w, uint32_t avail) {
+    if (avail < 7) return 0;
+    const uint32_t nd = w[1];
+    // the denominator's count sits at 4 + nd, its high word at 5 + nd
+    if (w[2] != 0 || nd > MC_MAX_WORDS - 7 || nd + 7 > avail) return 0;
+    const uint32_t dd = w[4 + nd];
+    if (w[5 + nd] != 0 || dd < 1 || dd > MC_MAX_WORDS - 6 - nd) return 0;
+    const uint32_t len = 6 + nd + dd;
+    return len <= avail ? len : 0;
+}
+
+// +-m * 2^e (m odd, non-zero) as a T, or false where no T has that value
+MC_FN bool mc_compose(uint64_t m, int e, bool neg, float* out) {
+    const int mbits = 64 - __builtin_clzll(m), top = e + mbits - 1;
+    if (mbits > 24 || e < -149 || top > 127) return false;
+    uint32_t bits = neg ? 0x80000000u : 0u;
+    if (top >= -126)
+        bits |= (uint32_t(top + 127) << 23) | ((uint32_t(m) << (24 - mbits)) & 0x7fffffu);
+    else
+        bits |= uint32_t(m) << (e + 149);  // subnormal
+    memcpy(out, &bits, sizeof bits);
+    return true;
+}
+
+MC_FN bool mc_compose(uint64_t m, int e, bool neg, double* out) {
+    const int mbits = 64 - __builtin_clzll(m), top = e + mbits - 1;
+    if (mbits > 53 || e < -1074 || top > 1023) return false;
+    uint64_t bits = neg ? uint64_t(1) << 63 : 0;
+    if (top >= -1022)
+        bits |= (uint64_t(top + 1023) << 52) | ((m << (53 - mbits)) & ((uint64_t(1) << 52) - 1));
+    else
+        bits |= m << (e + 1074);
+    memcpy(out, &bits, sizeof bits);
+    return true;
+}
+
+// the magnitude m << e must stay at or below 2^63 (2^31); only the negative
+// value reaches it
+MC_FN bool mc_compose(uint64_t m, int e, bool neg, int64_t* out) {
+    const int mbits = 64 - __builtin_clzll(m);
+    if (e < 0 || e + mbits > 64) return false;
+    const uint64_t mag = m << e;
+    if (mag > (uint64_t(1) << 63) || (!neg && mag == (uint64_t(1) << 63))) return false;
+    *out = int64_t(neg ? uint64_t(0) - mag : mag);
+    return true;
+}
+
+MC_FN bool mc_compose(uint64_t m, int e, bool neg, int32_t* out) {
+    const int mbits = 64 - __builtin_clzll(m);
+    if (e < 0 || e + mbits > 32) return false;
+    const uint64_t mag = m << e;
+    if (mag > (uint64_t(1) << 31) || (!neg && mag == (uint64_t(1) << 31))) return false;
+    *out = int32_t(uint32_t(neg ? uint64_t(0) - mag : mag));
+    return true;
+}
+
+// True exactly when the len words at w are the canonical element of some T:
+// what mc_write gives for mc_decompose of that value, which *out then is (+0
+// for the zero element). Reads w[0..len) only.
+template <typename T>
+MC_FN bool mc_read(const uint32_t* w, uint32_t len, T* out) {
+    if (len < 7 || len > MC_MAX_WORDS) return false;
+    const uint32_t sign = w[0], nd = w[1];
+    if (w[2] != 0 || nd > len - 7) return false;
+    const uint32_t dd = w[4 + nd];
+    // a Plus denominator of exactly the remaining words, no leading zero
+    if (w[3 + nd] != 2 || w[5 + nd] != 0 || dd != len - 6 - nd) return false;
+    const uint32_t* num = w + 3;
+    const uint32_t* den = w + 6 + nd;
+    const uint32_t dtop = den[dd - 1];
+    if (dtop == 0 || (dtop & (dtop - 1)) != 0) return false;  // one bit
+    for (uint32_t i = 0; i + 1 < dd; ++i)
+        if (den[i] != 0) return false;
+    const uint32_t k = 32 * (dd - 1) + uint32_t(__builtin_ctz(dtop));  // denominator 2^k
+    if (sign == 1) {  // NoSign: the zero element, 0 / 1
+        if (nd != 0 || k != 0) return false;
+        *out = T(0);
+        return true;
+    }
+    if ((sign != 0 && sign != 2) || nd == 0 || num[nd - 1] == 0) return false;
+    uint64_t m;
+    int e;
+    if (k == 0) {
+        // an integer m << e: zero digits, then m across up to three digits
+        uint32_t z = 0;
+        while (num[z] == 0) ++z;  // ends: the top digit is not zero
+        const uint32_t tz = uint32_t(__builtin_ctz(num[z]));
+        const int bits = 32 * int(nd - 1) + 32 - __builtin_clz(num[nd - 1]);
+        e = int(32 * z + tz);
+        if (bits - e > 64) return false;
+        const uint64_t lo = uint64_t(num[z]) | (z + 1 < nd ? uint64_t(num[z + 1]) << 32 : 0);
+        const uint64_t hi = z + 2 < nd ? num[z + 2] : 0;
+        m = tz ? (lo >> tz) | (hi << (64 - tz)) : lo;
+    } else {
+        // reduced: an odd numerator of at most two digits
+        if (nd > 2 || (num[0] & 1u) == 0) return false;
+        m = uint64_t(num[0]) | (nd == 2 ? uint64_t(num[1]) << 32 : 0);
+        e = -int(k);
+    }
+    return mc_compose(m, e, sign == 0, out);
+}

@@ -106,6 +106,33 @@ static auto codec_dispatch(const py::array& w, F f) {
     throw py::value_error("model dtype must be f32/f64/i32/i64");
 }
 
+// The strict decoder: the sequential walk over mc_span / mc_read that the K7d
+// kernels run in parallel. None unless the body is head 01, u64 n, exactly n
+// canonical elements of T and nothing after.
+template <typename T>
+static py::object codec_decode(const uint8_t* body, size_t nbytes) {
+    if (nbytes < 9 || body[0] != 1 || (nbytes - 9) % 4 != 0) return py::none();
+    uint64_t n;
+    std::memcpy(&n, body + 1, 8);
+    const uint64_t total = (nbytes - 9) / 4;
+    if (n > total / 7 || total > MC_MAX_WORDS * n) return py::none();
+    // elements start 1 mod 4 in the body: walk aligned words
+    std::vector<uint32_t> words(total);
+    if (total) std::memcpy(words.data(), body + 9, 4 * total);
+    py::array_t<T> out{py::ssize_t(n)};
+    T* dst = out.mutable_data();
+    uint64_t at = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t left = total - at;
+        const uint32_t len =
+            mc_span(words.data() + at, left > MC_MAX_WORDS ? MC_MAX_WORDS : uint32_t(left));
+        if (len == 0 || !mc_read<T>(words.data() + at, len, dst + i)) return py::none();
+        at += len;
+    }
+    if (at != total) return py::none();
+    return std::move(out);
+}
+
 void bind_sdk(py::module_& m) {
     auto s = m.def_submodule("sdk");
 
@@ -368,6 +395,23 @@ void bind_sdk(py::module_& m) {
             return py::bytes(body);
         });
     });
+    // The GPU's model decoder on the host: the weights of a canonical body
+    // (what model_codec_encode writes) as an ndarray of dtype 0..3, None for
+    // any other body. message/bincode.cpp's decoder accepts more: any rational.
+    s.def("model_codec_decode", [](py::buffer body, int dtype) -> py::object {
+        py::buffer_info bi = body.request();
+        if (!PyBuffer_IsContiguous(bi.view(), 'C'))
+            throw py::value_error("body must be C-contiguous");
+        const uint8_t* bp = static_cast<const uint8_t*>(bi.ptr);
+        const size_t blen = size_t(bi.size * bi.itemsize);
+        switch (dtype) {
+            case 0: return codec_decode<float>(bp, blen);
+            case 1: return codec_decode<double>(bp, blen);
+            case 2: return codec_decode<int32_t>(bp, blen);
+            case 3: return codec_decode<int64_t>(bp, blen);
+        }
+        throw py::value_error("dtype must be 0..3");
+    }, py::arg("body"), py::arg("dtype"));
     s.def("model_codec_words", [](const py::array& w) -> py::array_t<uint32_t> {
         return codec_dispatch(w, [](const auto* v, size_t n) {
             std::vector<uint32_t> words = codec_counts(v, n);

@@ -295,3 +295,20 @@ class CpuPlaneAggregator(MaskedAggregatorBase):
                 or weights.dtype not in self._MODEL_DTYPES:
             raise ValueError("encode_model takes a contiguous 1-D f32/f64/i32/i64 CPU tensor")
         return np.frombuffer(_core.sdk.encode_model(weights.numpy()), dtype=np.uint8)
+
+    def decode_model(self, body, dtype: int, tile_blocks: int = 0):
+        """The weights of an Option<Model> bincode body as a CPU tensor of
+        mask::DataType code `dtype`, or None unless the body is exactly what
+        encode_model writes for some weights of that dtype: the GPU engine's
+        contract, through the same element functions on the host. `body` is
+        any C-contiguous 1-D buffer (ValueError otherwise)."""
+        if dtype not in (0, 1, 2, 3):
+            raise ValueError("dtype must be 0..3")
+        try:
+            mv = memoryview(body)
+        except TypeError as e:
+            raise ValueError("decode_model takes a C-contiguous 1-D buffer") from e
+        if mv.ndim != 1 or not mv.c_contiguous:
+            raise ValueError("decode_model takes a C-contiguous 1-D buffer")
+        arr = _core.sdk.model_codec_decode(mv, dtype)
+        return None if arr is None else torch.from_numpy(arr)

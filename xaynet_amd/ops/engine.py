@@ -23,6 +23,8 @@ silent CPU fallback on a GPU box. Orders below 2^320 are supported; only the
 f64 Bmax orders (2112..2143 bits) are routed to the CPU oracle by the caller.
 """
 import os
+import warnings
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
@@ -63,6 +65,8 @@ class GpuMaskedAggregator(MaskedAggregatorBase):
         self._wire_pin = None  # cached pinned staging buffer of wire_object
         # encode_model: cached workspace, device body and pinned staging buffer
         self._enc_work = self._enc_dev = self._enc_pin = None
+        # decode_model: cached workspace, device body, output and pinned staging buffer
+        self._dec_work = self._dec_dev = self._dec_out = self._dec_pin = None
 
     # ---------------- tensor forms ----------------
 
@@ -391,6 +395,112 @@ class GpuMaskedAggregator(MaskedAggregatorBase):
             pin = self._enc_pin[: 3 + body]
             pin.copy_(out[: 3 + body])  # device to pinned host: synchronous
         return pin.numpy()[3:]
+
+    # ---------------- model body -> weights (K7d) ----------------
+
+    _MODEL_DTYPES = (torch.float32, torch.float64, torch.int32, torch.int64)
+    # how decode_model gets a host body across: "pinned" (host copies into two
+    # cached pinned chunks, overlapped with their DMAs), "pageable" (the runtime's staged
+    # copy) or "register" (_hip.host_register on the caller's buffer for the
+    # copy). scripts/model_decode_bench.py times all three; the fastest stays.
+    _DEC_STAGING = "pinned"
+
+    def decode_model(self, body, dtype: int, tile_blocks: int = 0):
+        """The weights of an Option<Model> bincode body, decoded on the GPU
+        (K7d), as a device tensor of mask::DataType code `dtype` (0=f32 1=f64
+        2=i32 3=i64): bit for bit what _core.sdk.decode_model gives for a body
+        that encode_model wrote. `body` is any C-contiguous 1-D buffer
+        (ValueError otherwise, before any launch). Returns None for every
+        other body: a wrong head or count, trailing bytes, an element that is
+        not the canonical form of a value of the dtype, more than 2^32
+        elements, or a body no device buffer takes. The tensor is a view of a
+        cached buffer, valid until the next call on this engine. tile_blocks
+        is a test hook (_hip._model_decode_plan)."""
+        if dtype not in (0, 1, 2, 3):
+            raise ValueError("dtype must be 0..3")
+        try:
+            mv = memoryview(body)
+        except TypeError as e:
+            raise ValueError("decode_model takes a C-contiguous 1-D buffer") from e
+        if mv.ndim != 1 or not mv.c_contiguous:
+            raise ValueError("decode_model takes a C-contiguous 1-D buffer")
+        src = np.frombuffer(mv, dtype=np.uint8)
+        nbytes = src.size
+        if nbytes < 9 or src[0] != 1 or (nbytes - 9) % 4:
+            return None
+        n = int.from_bytes(src[1:9].tobytes(), "little")
+        words = (nbytes - 9) // 4
+        if n > 2**32 or not 7 * n <= words <= 42 * n:
+            return None
+        tdt = self._MODEL_DTYPES[dtype]
+        if n == 0:
+            return torch.empty(0, dtype=tdt, device=self.acc.device)
+        with torch.cuda.device(self.acc.device):
+            try:
+                plan = _hip._model_decode_plan(words, tile_blocks)
+                work = self._enc_buffer("_dec_work", plan["work_bytes"])
+                dev = self._enc_buffer("_dec_dev", 3 + nbytes)
+                out = self._enc_buffer("_dec_out", n * 8)
+            except torch.OutOfMemoryError:
+                return None
+            self._upload_body(src, dev)
+            rejected = _hip._model_decode(dev.data_ptr() + 3, nbytes, dtype, n, work.data_ptr(),
+                                          out.data_ptr(), tile_blocks)
+        if rejected:
+            return None
+        return out[: n * tdt.itemsize].view(tdt)
+
+    def _upload_body(self, src: np.ndarray, dev: torch.Tensor, how: str | None = None):
+        """Host bytes -> dev[3:3 + len]: at byte 3 the body's words are aligned."""
+        how = how or self._DEC_STAGING
+        nbytes = src.size
+        if how == "pinned":
+            self._upload_pinned(src, dev)
+            return
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", UserWarning)  # a bytes body is read-only: only read
+            host = torch.from_numpy(src)
+        if how == "pageable":
+            dev[3 : 3 + nbytes].copy_(host)
+        elif how == "register":
+            _hip.host_register(src.ctypes.data, nbytes)
+            try:
+                dev[3 : 3 + nbytes].copy_(host)
+            finally:
+                _hip.host_unregister(src.ctypes.data)
+        else:
+            raise ValueError(f"unknown staging {how!r}")
+
+    # _upload_pinned: chunk size, and the host threads that fill one chunk
+    _DEC_CHUNK = 32 << 20
+    _DEC_COPY_THREADS = 4
+
+    def _upload_pinned(self, src: np.ndarray, dev: torch.Tensor):
+        """src -> dev[3:] through two cached pinned chunks: the host copy of
+        one chunk (a few threads; numpy copies without the GIL) runs while the
+        DMA of the chunk before it is in flight. Chunks are cut from the
+        device buffer's offsets, so both sides of every DMA are aligned alike."""
+        ch, end = self._DEC_CHUNK, 3 + src.size
+        if self._dec_pin is None:
+            self._dec_pin = (torch.empty((2, ch), dtype=torch.uint8, pin_memory=True),
+                             [torch.cuda.Event(), torch.cuda.Event()],
+                             ThreadPoolExecutor(self._DEC_COPY_THREADS))
+        pin, events, pool = self._dec_pin
+        for i, off in enumerate(range(0, end, ch)):
+            lo, hi = max(off, 3), min(off + ch, end)
+            slot, host = pin[i % 2], pin[i % 2].numpy()
+            events[i % 2].synchronize()  # the DMA that last read this chunk is done
+            if hi - lo < 1 << 20:  # not worth a hand-over to the threads
+                np.copyto(host[lo - off : hi - off], src[lo - 3 : hi - 3])
+            else:
+                step = -(-(hi - lo) // self._DEC_COPY_THREADS)
+                parts = [(a, min(a + step, hi)) for a in range(lo, hi, step)]
+                list(pool.map(lambda ab: np.copyto(host[ab[0] - off : ab[1] - off],
+                                                   src[ab[0] - 3 : ab[1] - 3]), parts))
+            dev[lo:hi].copy_(slot[lo - off : hi - off], non_blocking=True)
+            events[i % 2].record()
+        events[0].synchronize()
+        events[1].synchronize()
 
     def _enc_buffer(self, name: str, nbytes: int) -> torch.Tensor:
         """A cached device byte buffer of at least nbytes (contents not kept)."""

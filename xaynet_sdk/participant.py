@@ -71,22 +71,13 @@ class ParticipantABC(ABC):
         """Called before the participant thread stops."""
 
 
-_ACCELS = {}  # gpu_exact flag -> the process-wide ParticipantAccel
-
-
 class InternalParticipant(threading.Thread):
     def __init__(self, coordinator_url, participant, p_args, p_kwargs, state, scalar,
                  gpu=False, gpu_exact=False):
-        self._xaynet_participant = xaynet_sdk.Participant(coordinator_url, scalar, state)
-        if gpu:
-            from xaynet_amd.ops.accel import ParticipantAccel
-
-            # shared process-wide accelerators, one per flag value (engines
-            # cached per round config)
-            exact = bool(gpu_exact)
-            if exact not in _ACCELS:
-                _ACCELS[exact] = ParticipantAccel(exact=exact)
-            _ACCELS[exact].attach(self._xaynet_participant._inner)
+        # gpu=True: the shared process-wide accelerator (one per flag value)
+        # takes the masking and sum2 hooks and serves global_model_tensor()
+        self._xaynet_participant = xaynet_sdk.Participant(coordinator_url, scalar, state,
+                                                          gpu=gpu, gpu_exact=gpu_exact)
 
         # the user participant is constructed on the thread (run()) so the ML
         # model lives on the participant thread (reference participant.py:129-149)

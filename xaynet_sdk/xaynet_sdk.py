@@ -98,9 +98,26 @@ def _scalar_fraction(scalar: float):
 class Participant:
     """API-compatible wrapper of the native participant state machine."""
 
-    def __init__(self, coordinator_url: str, scalar: float = 1.0, state=None):
-        host, port = _parse_url(coordinator_url)
-        self._client = _core.rest.HttpXaynetClient(host, port)
+    def __init__(self, coordinator_url: str, scalar: float = 1.0, state=None, *,
+                 gpu: bool = False, gpu_exact: bool = False, client=None):
+        """gpu=True attaches the process-wide participant accelerator (update
+        masking and the sum2 mask sum on the GPU; gpu_exact as for
+        spawn_participant) and makes global_model_tensor() decode on the
+        device. client, an XaynetClient such as _core.sdk.InProcessClient,
+        replaces the HTTP client of coordinator_url, which is then unused."""
+        if client is None:
+            host, port = _parse_url(coordinator_url)
+            client = _core.rest.HttpXaynetClient(host, port)
+        self._client = client
+        self._accel = None
+        self._init_native(scalar, state)
+        if gpu:
+            from xaynet_amd.ops.accel import shared_accel
+
+            self._accel = shared_accel(gpu_exact)
+            self._accel.attach(self._inner)
+
+    def _init_native(self, scalar, state):
         num, den = _scalar_fraction(scalar)
         self._lock = threading.Lock()
         self._consumed = False
@@ -195,6 +212,27 @@ class Participant:
         if arr is None:
             return None
         return arr.tolist()
+
+    def global_model_tensor(self):
+        """The global model as a 1-D torch tensor of the round's data type, or
+        None while there is none: the values of global_model() without the
+        list. A gpu=True participant gets it on the accelerator's device,
+        decoded there from the fetched body; any other as a CPU tensor."""
+        import torch
+
+        self._check()
+        body = self._inner.global_model_bincode()
+        if body is None:
+            return None
+        dt = self._inner.model_data_type
+        if dt < 0:
+            raise GlobalModelUnavailable("round parameters unknown")
+        if self._accel is not None:
+            return self._accel.decode_model(body, dt)
+        arr = _core.sdk.decode_model(body, dt)
+        if arr is None:
+            return None
+        return torch.from_numpy(arr)
 
     def save(self) -> List[int]:
         """Serialize and consume the participant (reference semantics)."""
