@@ -24,7 +24,7 @@ def build(verbose=True, resource_usage=False):
     out = os.path.join(root, "xaynet_amd", f"_hip{ext}")
 
     # skip if up to date (kernels.h: the C ABI both sources include)
-    deps = src + [os.path.join(root, "xaynet_amd", "csrc", "gpu", h) for h in ("kernels.h", "limbs.h", "mask_quant.h", "model_codec.h", "u192.h", "k1_candidates_lds_body.inc",
+    deps = src + [os.path.join(root, "xaynet_amd", "csrc", "gpu", h) for h in ("kernels.h", "limbs.h", "mask_quant.h", "model_codec.h", "u192.h", "unmask_round.h", "k1_candidates_lds_body.inc",
                         "k1_candidates_lds_u128_body.inc")]
     if not resource_usage and os.path.exists(out) and all(os.path.getmtime(out) > os.path.getmtime(s) for s in deps):
         if verbose:

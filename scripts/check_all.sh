@@ -23,6 +23,10 @@ build/model_codec_sanitize
 g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
     -Ixaynet_amd/csrc scripts/model_decode_sanitize.cpp -o build/model_decode_sanitize
 build/model_decode_sanitize
+# the exact float unmask's element function (ur_round), float and double, L = 1..5
+g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
+    -Ixaynet_amd/csrc scripts/unmask_round_sanitize.cpp -o build/unmask_round_sanitize
+build/unmask_round_sanitize
 bash scripts/sanitize.sh
 bash scripts/tsan.sh
 

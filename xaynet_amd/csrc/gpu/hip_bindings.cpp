@@ -549,7 +549,9 @@ PYBIND11_MODULE(_hip, m) {
     // nb * add_shift * exp_shift as a decimal string: the shift is then
     // subtracted in integers (n_add_shift is unused), and `divisor`, where
     // exp_shift * scalar_sum is an exact integer below 2^64, makes integer
-    // outputs the exact truncated quotient.
+    // outputs the exact truncated quotient. A float dtype given offset and
+    // divisor (any size that fits the order's limbs) runs in exact mode: the
+    // rational (t - offset) / divisor rounded once to the output type.
     m.def(
         "unmask",
         [](uintptr_t planes, uintptr_t mask_lo, uintptr_t mask_hi, uintptr_t out, uint64_t len,
@@ -568,13 +570,15 @@ PYBIND11_MODULE(_hip, m) {
             } else if (off.n > o.n) {
                 throw py::value_error("the exact offset must be below the order");
             }
-            if (div.n > 1) throw py::value_error("divisor must be below 2^64");
+            const bool is_float = dtype == 0 || dtype == 1;
+            if (is_float ? div.n > o.n : div.n > 1)
+                throw py::value_error(is_float ? "the exact divisor must fit the order's limbs"
+                                               : "divisor must be below 2^64");
             // 1 / (exp_shift * scalar_sum), rounded to a double once
             const double scale = double(1.0L / (limbs_to_ld(e) * (long double)scalar_sum));
             check(xhip_k4_unmask_limbs(u64p(planes), u64p(mask_lo), u64p(mask_hi), dtype,
                                        reinterpret_cast<void*>(out), len, n_planes, digit_bits,
-                                       o.v, e.v, n_add_shift, scalar_sum, off.v, div.v.w[0],
-                                       scale),
+                                       o.v, e.v, n_add_shift, scalar_sum, off.v, div.v, scale),
                   "k4_unmask");
         },
         py::arg("planes"), py::arg("mask_lo"), py::arg("mask_hi"), py::arg("out"),
@@ -583,7 +587,8 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("digit_bits") = 32, py::arg("offset") = "", py::arg("divisor") = "", nogil);
 
     // u64 orders only: `vals` are plain u64 (cross-rank sums of) canonical
-    // values. `offset` and `divisor` as for unmask, for integer outputs.
+    // values. `offset` and `divisor` as for unmask: integer outputs, and float
+    // outputs in exact mode (both given).
     m.def(
         "unmask_values",
         [](uintptr_t vals, uintptr_t mask_lo, uintptr_t mask_hi, uintptr_t out, uint64_t len,

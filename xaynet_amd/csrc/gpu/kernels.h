@@ -111,7 +111,8 @@ hipError_t xhip_k4_unmask(const uint64_t* planes, const uint64_t* mask_lo,
 // u64 orders only: unmask (cross-rank sums of) canonical values. offset == 0:
 // the shift-in-doubles kernel. offset = nb * add_shift * exp_shift (integer
 // dtypes only): the exact-offset kernel of xhip_k4_unmask_limbs on one plane
-// of whole-word values, `divisor` as there.
+// of whole-word values, `divisor` as there. Float dtypes with an offset and a
+// divisor: the exact kernel (k4_unmask_exact), as there.
 hipError_t xhip_k4_unmask_values(const uint64_t* vals, const uint64_t* mask, int dtype,
                                  void* out, uint64_t len, uint64_t order, uint64_t exp_shift,
                                  double n_add_shift, double scalar_sum, uint64_t offset,
@@ -225,11 +226,16 @@ hipError_t xhip_k1_scatter_compact_limbs(const uint64_t* cand_lo, const uint64_t
 // 2^64 (else 0) - integer outputs are then exact - and `scale` the double
 // nearest 1/(exp_shift * scalar_sum). Integer dtypes need a one-word
 // exp_shift; u64 orders (L = 1) 32-bit digits.
+// Float dtypes with an offset AND a `divisor` (below 2^(64L), any limb count):
+// exact mode, L = 1..5 - the weight is the rational (t - offset) / divisor
+// rounded once to the output type in integers (unmask_round.h); exp_shift,
+// scalar_sum and scale are unused. Float outputs without a divisor keep the
+// kernels above.
 hipError_t xhip_k4_unmask_limbs(const uint64_t* planes, const uint64_t* mask_lo,
                                 const uint64_t* mask_hi, int dtype, void* out, uint64_t len,
                                 int n_planes, int digit_bits, xhip_limbs order,
                                 xhip_limbs exp_shift, double n_add_shift, double scalar_sum,
-                                xhip_limbs offset, uint64_t divisor, double scale);
+                                xhip_limbs offset, xhip_limbs divisor, double scale);
 hipError_t xhip_k2_canonicalize_limbs(const uint64_t* planes, uint64_t* out_lo,
                                       uint64_t* out_hi, uint64_t len, int n_planes,
                                       int digit_bits, xhip_limbs order);

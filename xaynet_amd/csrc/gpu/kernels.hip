@@ -38,6 +38,7 @@
 #include "mask_quant.h"
 #include "model_codec.h"
 #include "u192.h"
+#include "unmask_round.h"
 
 #include <algorithm>
 
@@ -1522,6 +1523,32 @@ __global__ void k4_unmask_offset(
     }
 }
 
+// K4, exact mode, float outputs, every width (L = 1..5): the front of
+// k4_unmask_offset - t, then |t - C| and its sign - and the exact rational
+// |t - C| / Q rounded once to OUT in integers (unmask_round.h), Q = exp_shift
+// * scalar_sum as limbs. No double is formed on the way. L = 1: `mask` is the
+// one row of u64 values, and `planes` may be one plane of u64 value sums.
+template <typename OUT, int L>
+__global__ void k4_unmask_exact(
+    const uint64_t* __restrict__ planes, const uint64_t* __restrict__ mask, int64_t mstride,
+    OUT* __restrict__ out, uint64_t len, int n_planes, int digit_bits, xhip_limbs order_c,
+    xhip_limbs offset_c, xhip_limbs divisor_c) {
+    uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= len) return;
+    const limbs<L> order = ml_from<L>(order_c);
+    limbs<L + 1> v = ml_from_planes<L + 1>(planes, len, i, n_planes, digit_bits);
+    limbs<L> t = ml_mod_sub<L>(ml_mod<L>(v, order), ml_load<L>(mask, mstride, i), order);
+    limbs<L> mag = ml_from<L>(offset_c);  // |t - C|
+    bool neg = !ml_geq(t, mag);
+    if (neg) {
+        ml_sub(mag, t);
+    } else {
+        ml_sub(t, mag);
+        mag = t;
+    }
+    out[i] = ur_round<OUT, L>(neg, mag, ml_from<L>(divisor_c));
+}
+
 // K5w for Bmax configs: y = scalar * w (one double rounding, clamped to
 // +-add_shift), q = floor(y * E) through the exact mantissa mul-shift — for
 // negative y that is -ceil(|y| * E) — and the masked value add_shift*E + q +
@@ -2266,7 +2293,13 @@ hipError_t xhip_k4_unmask_values(const uint64_t* vals, const uint64_t* mask, int
                                  xhip_limbs{{offset, 0, 0, 0, 0}}, exp_shift, divisor,
                                  scalar_sum, 0.0);
             } else {
-                return hipErrorInvalidValue;  // float outputs keep the double steps
+                // float outputs: exact mode with a divisor, else the double steps
+                if (!divisor || offset >= order) return hipErrorInvalidValue;
+                return launch_1d(k4_unmask_exact<OUT, 1>, len, vals, mask, int64_t(0),
+                                 static_cast<OUT*>(out), len, 1, 32,
+                                 xhip_limbs{{order, 0, 0, 0, 0}},
+                                 xhip_limbs{{offset, 0, 0, 0, 0}},
+                                 xhip_limbs{{divisor, 0, 0, 0, 0}});
             }
         }
         return launch_1d(k4_unmask_values<OUT, decltype(t)::trunc>, len, vals, mask,
@@ -2608,7 +2641,7 @@ hipError_t xhip_k4_unmask_limbs(const uint64_t* planes, const uint64_t* mask_lo,
                                 const uint64_t* mask_hi, int dtype, void* out, uint64_t len,
                                 int n_planes, int digit_bits, xhip_limbs order,
                                 xhip_limbs exp_shift, double n_add_shift, double scalar_sum,
-                                xhip_limbs offset, uint64_t divisor, double scale) {
+                                xhip_limbs offset, xhip_limbs divisor, double scale) {
     const int n = n_limbs_of(order);
     const bool exact_offset = n_limbs_of(offset) > 1 || offset.w[0] != 0;
     if (!exact_offset) {
@@ -2623,15 +2656,28 @@ hipError_t xhip_k4_unmask_limbs(const uint64_t* planes, const uint64_t* mask_lo,
         return hipErrorInvalidValue;
     const bool exp_is_word = n_limbs_of(exp_shift) == 1 && exp_shift.w[0] != 0;
     const int64_t mstride = n == 1 ? 0 : row_stride(mask_lo, mask_hi);
+    const int div_limbs = n_limbs_of(divisor);
+    const bool has_divisor = div_limbs > 1 || divisor.w[0] != 0;
     return dispatch_dtype(dtype, [&](auto t) {
         using OUT = typename decltype(t)::type;
         constexpr bool TRUNC = decltype(t)::trunc;
-        if (TRUNC && !exp_is_word) return hipErrorInvalidValue;
+        if constexpr (!TRUNC) {
+            // exact mode: a float output given its divisor
+            if (has_divisor) {
+                if (div_limbs > n) return hipErrorInvalidValue;
+                return dispatch_limbs<1>(n, [&](auto l) {
+                    return launch_1d(k4_unmask_exact<OUT, decltype(l)::value>, len, planes,
+                                     mask_lo, mstride, static_cast<OUT*>(out), len, n_planes,
+                                     digit_bits, order, offset, divisor);
+                });
+            }
+        }
+        if (TRUNC && (!exp_is_word || div_limbs > 1)) return hipErrorInvalidValue;
         return dispatch_limbs<1>(n, [&](auto l) {
             return launch_1d(k4_unmask_offset<OUT, TRUNC, decltype(l)::value>, len, planes,
                              mask_lo, mstride, static_cast<OUT*>(out), len, n_planes,
-                             digit_bits, order, offset, exp_shift.w[0], divisor, scalar_sum,
-                             scale);
+                             digit_bits, order, offset, exp_shift.w[0], divisor.w[0],
+                             scalar_sum, scale);
         });
     });
 }

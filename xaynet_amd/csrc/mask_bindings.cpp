@@ -5,6 +5,7 @@
 
 #include "gpu/mask_quant.h"
 #include "gpu/u192.h"
+#include "gpu/unmask_round.h"
 #include "mask/masking.h"
 
 namespace py = pybind11;
@@ -165,8 +166,75 @@ static py::list planes_mod(const py::array& planes, const py::int_& order, int d
     }
 }
 
+// ---- unmask_round: the exact float unmask's element function
+// (gpu/unmask_round.h) on the host
+
+static bool int_to_limbs(const py::int_& v, xhip_limbs& out) {
+    if (v < py::int_(0) || v.attr("bit_length")().cast<int>() > 64 * ML_MAX_LIMBS) return false;
+    const std::string raw = v.attr("to_bytes")(8 * ML_MAX_LIMBS, "little").cast<std::string>();
+    for (int j = 0; j < ML_MAX_LIMBS; ++j) {
+        out.w[j] = 0;
+        for (int b = 7; b >= 0; --b) out.w[j] = (out.w[j] << 8) | uint8_t(raw[8 * j + b]);
+    }
+    return true;
+}
+
+template <typename F, int L>
+static py::array unmask_round_as(const std::vector<xhip_limbs>& mags,
+                                 const std::vector<bool>& negs, const xhip_limbs& q) {
+    py::array_t<F> out(py::ssize_t(mags.size()));
+    F* o = out.mutable_data();
+    for (size_t i = 0; i < mags.size(); ++i)
+        o[i] = ur_round<F, L>(negs[i], ml_from<L>(mags[i]), ml_from<L>(q));
+    return out;
+}
+
+template <typename F>
+static py::array unmask_round_typed(int L, const std::vector<xhip_limbs>& mags,
+                                    const std::vector<bool>& negs, const xhip_limbs& q) {
+    switch (L) {
+        case 1: return unmask_round_as<F, 1>(mags, negs, q);
+        case 2: return unmask_round_as<F, 2>(mags, negs, q);
+        case 3: return unmask_round_as<F, 3>(mags, negs, q);
+        case 4: return unmask_round_as<F, 4>(mags, negs, q);
+        default: return unmask_round_as<F, 5>(mags, negs, q);
+    }
+}
+
+// The float (dtype 0: f32, 1: f64) nearest to mags[i] / q, ties to even,
+// negative where negs[i], as a numpy array: ur_round<F, L> at `limbs` = L
+// limbs, by default the fewest that hold q and every magnitude.
+static py::array unmask_round(const py::sequence& mags, const py::sequence& negs,
+                              const py::int_& q, int dtype, int n_limbs) {
+    if (dtype != 0 && dtype != 1) throw py::value_error("unmask_round: dtype is 0 (f32) or 1 (f64)");
+    if (py::len(mags) != py::len(negs))
+        throw py::value_error("unmask_round: one sign per magnitude");
+    xhip_limbs qv;
+    if (q <= py::int_(0) || !int_to_limbs(q, qv))
+        throw py::value_error("unmask_round: q in [1, 2^320)");
+    std::vector<xhip_limbs> mv(py::len(mags));
+    std::vector<bool> nv(mv.size());
+    int need = 1;
+    for (int j = 1; j < ML_MAX_LIMBS; ++j)
+        if (qv.w[j]) need = j + 1;
+    for (size_t i = 0; i < mv.size(); ++i) {
+        if (!int_to_limbs(py::int_(mags[i]), mv[i]))
+            throw py::value_error("unmask_round: magnitudes in [0, 2^320)");
+        for (int j = need; j < ML_MAX_LIMBS; ++j)
+            if (mv[i].w[j]) need = j + 1;
+        nv[i] = py::cast<bool>(negs[i]);
+    }
+    if (n_limbs == 0) n_limbs = need;
+    if (n_limbs < need || n_limbs > ML_MAX_LIMBS)
+        throw py::value_error("unmask_round: limbs must hold q and every magnitude (at most 5)");
+    return dtype == 0 ? unmask_round_typed<float>(n_limbs, mv, nv, qv)
+                      : unmask_round_typed<double>(n_limbs, mv, nv, qv);
+}
+
 void bind_mask(py::module_& m) {
     auto mm = m.def_submodule("mask");
+    mm.def("unmask_round", &unmask_round, py::arg("mags"), py::arg("negs"), py::arg("q"),
+           py::arg("dtype"), py::arg("limbs") = 0);
     mm.def("planes_mod", &planes_mod, py::arg("planes"), py::arg("order"), py::arg("digit_bits"),
            py::arg("path") = "ml", py::arg("runtime_shift") = false);
     mm.def("quantize_exact", &quantize_exact, py::arg("weights"), py::arg("cfg"), py::arg("num"),
@@ -322,6 +390,14 @@ void bind_mask(py::module_& m) {
         .def("validate_unmasking",
              [](const Aggregation& a, const MaskObject& o) { return int(a.validate_unmasking(o)); })
         .def("set", &Aggregation::set, py::arg("object"), py::arg("nb_models"))
+        // tests: the unmasked model as the exact rationals themselves, one
+        // (numerator, denominator) pair of decimal strings per weight
+        .def("unmask_rationals", [](const Aggregation& a, const MaskObject& mask_obj) {
+            py::list out;
+            for (const Rational& r : a.unmask(mask_obj))
+                out.append(py::make_tuple(r.numer.to_dec(), r.denom.to_dec()));
+            return out;
+        })
         .def("unmask", [](const Aggregation& a, const MaskObject& mask_obj) -> py::object {
             RationalModel rm = a.unmask(mask_obj);
             switch (a.config().vect.dtype) {

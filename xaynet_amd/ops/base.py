@@ -231,6 +231,11 @@ class MaskedAggregatorBase:
         div = Fraction(vinfo["exp_shift_u64"] * (n1 - nb * int(info["add_shift"]) * exp1), exp1)
         if div.denominator == 1 and 0 < div < 2**64:
             vinfo["divisor"] = int(div)
+        # the same integer at any size the config's limbs hold: what the
+        # exact float unmask divides by (exact_divisor)
+        vinfo["exact_divisor"] = None
+        if div.denominator == 1 and 0 < div < 2**(64 * self.n_limbs):
+            vinfo["exact_divisor"] = int(div)
         return scalar_sum, vinfo, dt
 
     def exact_integers(self, vinfo, dt: int) -> bool:
@@ -239,3 +244,23 @@ class MaskedAggregatorBase:
         vect configs have). Float outputs keep the double steps."""
         return (not self.bmax and dt in (2, 3) and vinfo["divisor"] is not None
                 and vinfo["exp_shift_u64"] < 2**64)
+
+    def exact_divisor(self, vinfo, dt: int) -> int | None:
+        """What unmask(..., exact=True) needs, or ValueError where exact mode
+        does not apply. Float outputs: Q = exp_shift * scalar_sum, a positive
+        integer that fits the config's limbs; the weight is then (t - offset)
+        / Q rounded once. Integer outputs: None - the default path is already
+        the exact truncated quotient, but only with an exact one-word divisor
+        (Bmax, or `exact_integers`); with the double steps alone exact mode is
+        refused."""
+        if dt in (0, 1):
+            if vinfo["exact_divisor"] is None:
+                raise ValueError(
+                    "exact unmask needs exp_shift * scalar_sum to be a positive integer below "
+                    f"2^{64 * self.n_limbs} (the same exp_shift for the vector and the unit "
+                    "config, and a positive scalar sum)")
+            return vinfo["exact_divisor"]
+        if vinfo["divisor"] is None or not (self.bmax or self.exact_integers(vinfo, dt)):
+            raise ValueError("exact unmask of an integer model needs exp_shift * scalar_sum to "
+                             "be an integer below 2^64; only the double steps apply here")
+        return None

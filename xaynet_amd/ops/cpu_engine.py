@@ -222,15 +222,21 @@ class CpuPlaneAggregator(MaskedAggregatorBase):
         return out_planes
 
     def _finalize(self, masked: np.ndarray, mask_values: torch.Tensor, mask_unit: int, nb: int,
-                  dtype: int | None) -> torch.Tensor:
+                  dtype: int | None, exact: bool = False) -> torch.Tensor:
         """masked: object-int array of canonical values."""
         scalar_sum, vinfo, dt = self._unmask_scalars(mask_unit, nb, dtype)
+        q = self.exact_divisor(vinfo, dt) if exact else None
         order = self.order_int
         t = (masked + order - self._ints(mask_values)) % order
         exp = vinfo["exp_shift_u64"]
         n_add = nb * vinfo["add_shift"]
         # the exact-offset K4: d = t - nb*add*E as a signed integer
         d = [int(v) - vinfo["offset"] for v in t]
+        if q is not None:
+            # exact mode, float outputs: d / Q rounded once, by the element
+            # function the kernel compiles (gpu/unmask_round.h)
+            return torch.from_numpy(_core.mask.unmask_round(
+                [abs(v) for v in d], [v < 0 for v in d], q, dt, limbs=self.n_limbs))
         if dt in (2, 3) and vinfo["divisor"] and (self.bmax or self.exact_integers(vinfo, dt)):
             # exact truncated quotient, never through doubles; the low 64
             # bits wrap into the output type as the kernel's casts do
@@ -259,22 +265,29 @@ class CpuPlaneAggregator(MaskedAggregatorBase):
         return torch.from_numpy(outf.astype(np_dt))
 
     def unmask(self, mask_values: torch.Tensor, mask_unit: int,
-               nb_models: int | None = None, dtype: int | None = None) -> torch.Tensor:
+               nb_models: int | None = None, dtype: int | None = None,
+               exact: bool = False) -> torch.Tensor:
         nb = self.nb_models if nb_models is None else nb_models
-        return self._finalize(self._planes_to_ints(self.acc), mask_values, mask_unit, nb, dtype)
+        return self._finalize(self._planes_to_ints(self.acc), mask_values, mask_unit, nb, dtype,
+                              exact)
+
+    def unmask_f32(self, mask_values: torch.Tensor, mask_unit: int,
+                   nb_models: int | None = None, exact: bool = False) -> torch.Tensor:
+        return self.unmask(mask_values, mask_unit, nb_models=nb_models, dtype=0, exact=exact)
 
     def unmask_values(self, vals: torch.Tensor, mask_values: torch.Tensor, mask_unit: int,
-                      nb_models: int, dtype: int | None = None) -> torch.Tensor:
+                      nb_models: int, dtype: int | None = None,
+                      exact: bool = False) -> torch.Tensor:
         if self.wide:
             raise NotImplementedError("values unmask covers u64 orders")
         masked = vals.numpy().view(_U64).astype(object) % self.order_int
-        return self._finalize(masked, mask_values, mask_unit, nb_models, dtype)
+        return self._finalize(masked, mask_values, mask_unit, nb_models, dtype, exact)
 
     def unmask_planes(self, planes: torch.Tensor, mask_values: torch.Tensor, mask_unit: int,
                       nb_models: int, dtype: int | None = None,
-                      digit_bits: int = 32) -> torch.Tensor:
+                      digit_bits: int = 32, exact: bool = False) -> torch.Tensor:
         return self._finalize(self._planes_to_ints(planes, digit_bits), mask_values, mask_unit,
-                              nb_models, dtype)
+                              nb_models, dtype, exact)
 
     # ---------------- wire format ----------------
 

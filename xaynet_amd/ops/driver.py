@@ -31,9 +31,12 @@ LOG = logging.getLogger("xaynet.gpu_driver")
 
 class GpuCoordinatorDriver(threading.Thread):
     def __init__(self, coordinator, vect_cfg, unit_cfg, length: int,
-                 device: str = "cuda:0", pool_size: int = 512, poll_s: float = 0.002):
+                 device: str = "cuda:0", pool_size: int = 512, poll_s: float = 0.002,
+                 exact_unmask: bool = False):
         super().__init__(daemon=True)
         self.coordinator = coordinator
+        # publish the exact rational weights rounded once (engine exact mode)
+        self.exact_unmask = bool(exact_unmask)
         self.eng = GpuMaskedAggregator(vect_cfg, unit_cfg, length, device=device)
         self.length = length
         self.pool_size = pool_size
@@ -92,12 +95,20 @@ class GpuCoordinatorDriver(threading.Thread):
         mask_vect, mask_unit = self._split_mask_object(mask_bytes)
         t = torch.frombuffer(bytearray(mask_vect), dtype=torch.uint8).to(self.eng.device)
         mask_vals = self.eng.unpack_wire(t)
-        out = self.eng.unmask(mask_vals, mask_unit, nb_models=nb_models)
+        out = self._unmask(mask_vals, mask_unit, nb_models)
         # K7: the body is encoded on the GPU and lands in pinned host memory;
         # the coordinator copies that view once, into its own storage
         self.coordinator.supply_unmasked_model(self.eng.encode_model(out))
         self.eng.reset()
         self.rounds_unmasked += 1
+
+    def _unmask(self, mask_vals, mask_unit: int, nb_models: int):
+        if self.exact_unmask:
+            try:
+                return self.eng.unmask(mask_vals, mask_unit, nb_models=nb_models, exact=True)
+            except ValueError as e:
+                LOG.warning("exact unmask refused (%s); default unmask this round", e)
+        return self.eng.unmask(mask_vals, mask_unit, nb_models=nb_models)
 
     # ------------------------------------------------------------- loop
 

@@ -211,21 +211,30 @@ class GpuMaskedAggregator(MaskedAggregatorBase):
         return out_planes
 
     def unmask(self, mask_values: torch.Tensor, mask_unit: int,
-               nb_models: int | None = None, dtype: int | None = None) -> torch.Tensor:
+               nb_models: int | None = None, dtype: int | None = None,
+               exact: bool = False) -> torch.Tensor:
         """Unmask the aggregate into model weights (reference unmask math,
         masking.rs:190-231). dtype follows mask::DataType (default: the vect
-        config's data type); integers truncate toward zero."""
+        config's data type); integers truncate toward zero. Float outputs
+        carry the double roundings of K4 (tests/unmask_edges.float_bound);
+        exact=True returns the exact rational weight rounded once to the
+        output type instead (k4_unmask_exact), for every order the engine
+        covers - ValueError where exp_shift * scalar_sum is no positive
+        integer that fits the order's limbs, or where an integer dtype would
+        only get the double steps (`exact_divisor`)."""
         nb = self.nb_models if nb_models is None else nb_models
-        return self.unmask_planes(self.acc, mask_values, mask_unit, nb, dtype)
+        return self.unmask_planes(self.acc, mask_values, mask_unit, nb, dtype, exact=exact)
 
     def unmask_f32(self, mask_values: torch.Tensor, mask_unit: int,
-                   nb_models: int | None = None) -> torch.Tensor:
-        return self.unmask(mask_values, mask_unit, nb_models=nb_models, dtype=0)
+                   nb_models: int | None = None, exact: bool = False) -> torch.Tensor:
+        return self.unmask(mask_values, mask_unit, nb_models=nb_models, dtype=0, exact=exact)
 
     def unmask_values(self, vals: torch.Tensor, mask_values: torch.Tensor, mask_unit: int,
-                      nb_models: int, dtype: int | None = None) -> torch.Tensor:
+                      nb_models: int, dtype: int | None = None,
+                      exact: bool = False) -> torch.Tensor:
         """Unmask a u64 tensor of (possibly cross-rank summed) canonical
-        values — the reduce-scatter path. Valid while nb_ranks*order < 2^64."""
+        values — the reduce-scatter path. Valid while nb_ranks*order < 2^64.
+        exact as for unmask."""
         if self.wide:
             raise NotImplementedError("values unmask covers u64 orders")
         v_ptr, _, n = self._vals(vals)
@@ -233,32 +242,48 @@ class GpuMaskedAggregator(MaskedAggregatorBase):
         if n != nm:
             raise ValueError("unmask_values: lengths differ")
         scalar_sum, vinfo, dt = self._unmask_scalars(mask_unit, nb_models, dtype)
+        q = self.exact_divisor(vinfo, dt) if exact else None
         out = torch.empty(n, dtype=self._TORCH_DTYPES[dt], device=vals.device)
-        exact = self.exact_integers(vinfo, dt)
+        if q is not None:  # a float output in exact mode
+            _hip.unmask_values(v_ptr, lo, hi, out.data_ptr(), n, self.order,
+                               str(vinfo["exp_shift_u64"]), 0.0, scalar_sum, dt,
+                               offset=str(vinfo["offset"]), divisor=str(q))
+            return out
+        offset = self.exact_integers(vinfo, dt)
         _hip.unmask_values(v_ptr, lo, hi, out.data_ptr(), n, self.order,
                            str(vinfo["exp_shift_u64"]), nb_models * vinfo["add_shift"],
-                           scalar_sum, dt, offset=str(vinfo["offset"]) if exact else "",
-                           divisor=str(vinfo["divisor"]) if exact else "")
+                           scalar_sum, dt, offset=str(vinfo["offset"]) if offset else "",
+                           divisor=str(vinfo["divisor"]) if offset else "")
         return out
 
     def unmask_planes(self, planes: torch.Tensor, mask_values: torch.Tensor, mask_unit: int,
                       nb_models: int, dtype: int | None = None,
-                      digit_bits: int = 32) -> torch.Tensor:
+                      digit_bits: int = 32, exact: bool = False) -> torch.Tensor:
         """Unmask a contiguous [k, n] digit-plane tensor (e.g. this rank's
         reduce-scattered shard) against matching mask values, which may be a
         slice mask[lo:lo+n] / mask[:, lo:lo+n]. Wide orders take planes of
-        digit_bits-wide digits."""
+        digit_bits-wide digits. exact as for unmask."""
         lo, hi, n = self._vals(mask_values)
         ptr, k = self._planes(planes, n, read_bits=digit_bits)
         scalar_sum, vinfo, dt = self._unmask_scalars(mask_unit, nb_models, dtype)
+        q = self.exact_divisor(vinfo, dt) if exact else None
         out = torch.empty(n, dtype=self._TORCH_DTYPES[dt], device=planes.device)
+        if q is not None:
+            # a float output in exact mode: offset and divisor as integers,
+            # the quotient rounded once in the kernel
+            _hip.unmask(ptr, lo, hi, out.data_ptr(), n, k, self.order,
+                        str(vinfo["exp_shift_u64"]), 0.0, scalar_sum, dt, digit_bits,
+                        offset=str(vinfo["offset"]), divisor=str(q))
+            return out
         if self.bmax or self.exact_integers(vinfo, dt):
             # nb*add_shift is subtracted as the exact integer offset, not as
             # a double: Bmax weights would vanish against it, and integer
             # outputs of the other bounds are the exact truncated quotient
+            # (the divisor is theirs: given one, a float output runs exact mode)
+            divisor = str(vinfo["divisor"] or "") if dt in (2, 3) else ""
             _hip.unmask(ptr, lo, hi, out.data_ptr(), n, k, self.order,
                         str(vinfo["exp_shift_u64"]), 0.0, scalar_sum, dt, digit_bits,
-                        offset=str(vinfo["offset"]), divisor=str(vinfo["divisor"] or ""))
+                        offset=str(vinfo["offset"]), divisor=divisor)
             return out
         _hip.unmask(ptr, lo, hi, out.data_ptr(), n, k, self.order, str(vinfo["exp_shift_u64"]),
                     nb_models * vinfo["add_shift"], scalar_sum, dt, digit_bits)

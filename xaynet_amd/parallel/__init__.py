@@ -132,14 +132,20 @@ class ShardedAggregation:
         return mask_partial
 
     def unmask_global(self, mask_total: torch.Tensor, unit_mask_total: int,
-                      nb_models: int) -> torch.Tensor:
-        """Cross-rank reduce + unmask; returns the full model on every rank."""
+                      nb_models: int, exact: bool = False) -> torch.Tensor:
+        """Cross-rank reduce + unmask; returns the full model on every rank.
+        exact is the engine's exact unmask mode, whatever the strategy: the
+        refusal (ValueError) depends on the unit sum and the config alone, so
+        every rank raises it or none does, before any collective."""
         eng, dist = self.eng, self.dist
+        if exact:
+            _, vinfo, dt = eng._unmask_scalars(unit_mask_total, nb_models)
+            eng.exact_divisor(vinfo, dt)
         if self.strategy == "single":
-            return eng.unmask(mask_total, unit_mask_total, nb_models=nb_models)
+            return eng.unmask(mask_total, unit_mask_total, nb_models=nb_models, exact=exact)
         if self.strategy == "all_reduce":
             dist.all_reduce(eng.acc)
-            return eng.unmask(mask_total, unit_mask_total, nb_models=nb_models)
+            return eng.unmask(mask_total, unit_mask_total, nb_models=nb_models, exact=exact)
         shard, lo = self._shard, self.rank * self._shard
         out_full = self._scratch("out_full", eng.length,
                                  dtype=eng._TORCH_DTYPES[eng.vect_cfg.dtype])
@@ -148,7 +154,7 @@ class ShardedAggregation:
             vals_shard = self._scratch("vals_shard", shard)
             dist.reduce_scatter_tensor(vals_shard, canon)
             out_shard = eng.unmask_values(vals_shard, mask_total[lo:lo + shard],
-                                          unit_mask_total, nb_models)
+                                          unit_mask_total, nb_models, exact=exact)
         elif self.strategy == "digits_rs":
             k, w = self._digits
             compact = eng.recode_planes(self._scratch("compact", k, eng.length), w)
@@ -156,12 +162,13 @@ class ShardedAggregation:
             for d in range(k):
                 dist.reduce_scatter_tensor(shard_planes[d], compact[d])
             out_shard = eng.unmask_planes(shard_planes, mask_total[:, lo:lo + shard],
-                                          unit_mask_total, nb_models, digit_bits=w)
+                                          unit_mask_total, nb_models, digit_bits=w,
+                                          exact=exact)
         else:  # planes_rs
             shard_planes = self._scratch("shard_planes", eng.n_digits, shard)
             for d in range(eng.n_digits):
                 dist.reduce_scatter_tensor(shard_planes[d], eng.acc[d])
             out_shard = eng.unmask_planes(shard_planes, mask_total[lo:lo + shard],
-                                          unit_mask_total, nb_models)
+                                          unit_mask_total, nb_models, exact=exact)
         dist.all_gather_into_tensor(out_full, out_shard)
         return out_full

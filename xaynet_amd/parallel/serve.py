@@ -131,7 +131,7 @@ def _worker_main(rank: int, world: int, device_kind: str, cfg_args, length: int,
                 received += len(cmd[1])
                 stage_and_aggregate(cmd[1])
             elif op == "unmask":
-                _, mask_slot, mask_unit, unit_acc, nb_models, round_id = cmd
+                _, mask_slot, mask_unit, unit_acc, nb_models, round_id, exact = cmd
                 off = mask_slot * sbytes
                 packed = host_t[off : off + row_bytes]
                 if device_kind == "cuda":
@@ -140,7 +140,15 @@ def _worker_main(rank: int, world: int, device_kind: str, cfg_args, length: int,
                 del packed  # drop the ring-slice view (shm must close cleanly)
                 free_conn.send(mask_slot)
                 eng.unit_acc = unit_acc
-                out = sharded.unmask_global(mask_vals, mask_unit, nb_models)
+                try:
+                    out = sharded.unmask_global(mask_vals, mask_unit, nb_models, exact=exact)
+                except ValueError as e:
+                    if not exact:
+                        raise
+                    # raised on every rank alike, before any collective
+                    if rank == 0:
+                        LOG.warning("exact unmask refused (%s); default unmask this round", e)
+                    out = sharded.unmask_global(mask_vals, mask_unit, nb_models)
                 local_n = eng.nb_models
                 eng.reset()
                 received = 0
@@ -307,9 +315,11 @@ class ServePlane:
     # ---- unmask ----
 
     def unmask(self, mask_vect: bytes, mask_unit: int, unit_acc: int, nb_models: int,
-               round_id: int, timeout: float = 600.0):
+               round_id: int, timeout: float = 600.0, exact: bool = False):
         """Broadcast the winning mask, run the collective unmask, return the
-        unmasked weights (numpy array) from rank 0."""
+        unmasked weights (numpy array) from rank 0. exact asks the workers for
+        the engine's exact unmask mode; where it does not apply they log it
+        and unmask by default."""
         self.flush()
         for r in range(self.world):
             with self._wlocks[r]:
@@ -318,7 +328,7 @@ class ServePlane:
                 self.views[r][off : off + len(mask_vect)] = self._np.frombuffer(
                     mask_vect, dtype=self._np.uint8)
                 self.cmd_conns[r].send(
-                    ("unmask", slot, mask_unit, unit_acc, nb_models, round_id))
+                    ("unmask", slot, mask_unit, unit_acc, nb_models, round_id, bool(exact)))
         model = None
         total_n = 0
         for _ in range(self.world):
@@ -377,11 +387,13 @@ class MultiGpuServeDriver(threading.Thread):
 
     def __init__(self, coordinator, vect_cfg, unit_cfg, length: int,
                  n_workers: int, device_kind: str = "cuda",
-                 slots_per_worker: int = 32, batch: int = 16, poll_s: float = 0.002):
+                 slots_per_worker: int = 32, batch: int = 16, poll_s: float = 0.002,
+                 exact_unmask: bool = False):
         super().__init__(daemon=True)
         self.coordinator = coordinator
         self.length = length
         self.poll_s = poll_s
+        self.exact_unmask = bool(exact_unmask)
         self._vect_bpn = vect_cfg.bytes_per_number
         self._unit_bpn = unit_cfg.bytes_per_number
         self._unit_order = int(unit_cfg.order)
@@ -492,7 +504,7 @@ class MultiGpuServeDriver(threading.Thread):
         mask_vect, mask_unit = self._split_mask_object(mask_bytes)
         weights = self.plane.unmask(
             mask_vect, mask_unit, self._unit_acc, nb_models,
-            round_id=int(self.coordinator.round_id))
+            round_id=int(self.coordinator.round_id), exact=self.exact_unmask)
         body = _core.sdk.encode_model(weights)
         self.coordinator.supply_unmasked_model(body)
         self._unit_acc = 0

@@ -105,12 +105,14 @@ def serve(settings: Settings, ready_event: threading.Event | None = None,
             from xaynet_amd.parallel.serve import MultiGpuServeDriver
 
             driver = MultiGpuServeDriver(coordinator, c, c, settings.model_length,
-                                         n_workers=n, device_kind="cuda")
+                                         n_workers=n, device_kind="cuda",
+                                         exact_unmask=settings.gpu_exact_unmask)
             LOG.info("multi-GPU serve plane: %d devices", n)
         else:
             from xaynet_amd.ops import make_coordinator_driver
 
-            driver = make_coordinator_driver(coordinator, c, c, settings.model_length)
+            driver = make_coordinator_driver(coordinator, c, c, settings.model_length,
+                                             exact_unmask=settings.gpu_exact_unmask)
         driver.start()
     host, port = settings.bind_host_port()
     if settings.api.tls_certificate:

@@ -95,6 +95,7 @@ class Settings:
     s3_bucket: str = "global-models"
     gpu: bool = False                   # aggregate on the MI355X data plane
     gpu_devices: int = 0                # 0 = all visible GPUs; N = use N devices
+    gpu_exact_unmask: bool = False      # float weights: the exact rational, rounded once
 
     # ------------------------------------------------------------ loading
 
@@ -154,6 +155,7 @@ class Settings:
         gpu = raw.get("gpu", {})
         s.gpu = bool(gpu.get("enable", False))
         s.gpu_devices = int(gpu.get("devices", 0))
+        s.gpu_exact_unmask = bool(gpu.get("exact_unmask", False))
         return s
 
     # ---------------------------------------------------------- validation
