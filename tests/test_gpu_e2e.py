@@ -152,3 +152,28 @@ def test_full_round_multigpu_serve_plane_cuda_worker():
     assert np.isfinite(model).all()
     assert np.abs(model).max() <= 1.0 + 1e-5
     assert np.abs(model).mean() > 1e-3
+
+
+def test_serve_plane_cuda_worker_batches_and_rounds():
+    """A CUDA worker fed more updates than its pool has rows and its ring has
+    slots, with an odd batch: every group goes slot -> pinned row -> pool row
+    -> K3, the pool and the pinned rows are reused group after group, and a
+    second round runs through the same plane. Same oracle and bound as the
+    CPU-worker rounds of tests/test_serve_plane.py."""
+    _gpu()
+    from test_serve_plane import CFG_ARGS, _forge_round
+
+    from xaynet_amd.parallel.serve import ServePlane
+
+    length, k = 10_003, 11
+    plane = ServePlane(CFG_ARGS, length, 1, "cuda", slots_per_worker=8, batch=3)
+    try:
+        for rid, (seed0, rng_seed) in enumerate([(1, 7), (50, 11)], 1):
+            weights, updates, unit_acc, mask_vect, mask_unit = _forge_round(
+                length, k, seed0=seed0, rng_seed=rng_seed)
+            for v in updates:
+                plane.put_update(v)
+            out = plane.unmask(mask_vect, mask_unit, unit_acc, k, round_id=rid)
+            assert np.abs(out - np.mean(weights, axis=0)).max() < 1e-6
+    finally:
+        plane.stop()

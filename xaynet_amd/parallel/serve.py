@@ -1,14 +1,16 @@
-"""Multi-GPU serve plane: per-device worker processes fed by a pinned
+"""Multi-GPU serve plane: per-device worker processes fed by a
 shared-memory ingest ring, composed with ShardedAggregation at unmask.
 
 This makes `python -m xaynet_amd.server` itself multi-GPU (VERDICT r01 item
 1): the coordinator's protocol thread stages validated masked updates (wire
 bytes); the `MultiGpuServeDriver` thread drains them, writes the vector limbs
 into per-worker shared-memory slots and round-robins batches across one
-worker process per GPU. Each worker pins the shm mapping (hipHostRegister),
-double-buffers async H2D copies on a copy stream overlapped with K3
-aggregation on the compute stream (the productized ingest
-pipeline — no synchronous pageable copies), and at Unmask the workers run
+worker process per GPU. Each worker moves its slots through two pinned rows
+of its own (allocated pinned; no hipHostRegister of the shm mapping, which a
+VM guest refuses): the host copy of one row overlaps the async H2D copy of
+the other on a copy stream, ahead of K3 aggregation on the compute stream
+(the productized ingest pipeline — no synchronous pageable
+copies), and at Unmask the workers run
 `ShardedAggregation.unmask_global` over RCCL/xGMI; rank 0 ships the unmasked
 model back to the coordinator.
 
@@ -74,16 +76,21 @@ def _worker_main(rank: int, world: int, device_kind: str, cfg_args, length: int,
             dist = tdist
 
         if device_kind == "cuda":
-            from xaynet_amd import _hip
             from xaynet_amd.ops import GpuMaskedAggregator
 
             torch.cuda.set_device(rank)
             eng = GpuMaskedAggregator(vect_cfg, unit_cfg, length, device=f"cuda:{rank}")
-            # pin the whole ring once: H2D from it becomes true async DMA
-            _hip.host_register(host.ctypes.data, host.nbytes)
             host_t = torch.from_numpy(host)
+            # the ring is another process's shm mapping and cannot be
+            # allocated pinned, and pinning an existing mapping
+            # (hipHostRegister) is not available on every host (a VM guest
+            # refuses it). Rows go through two pinned rows instead: the host
+            # copy of one overlaps the async DMA of the other.
+            stage = torch.empty((2, length * eng.bpn), dtype=torch.uint8, pin_memory=True)
+            stage_free = [torch.cuda.Event(), torch.cuda.Event()]
             copy_stream = torch.cuda.Stream(device=eng.device)
             copy_done = torch.cuda.Event()
+            agg_done = torch.cuda.Event()
         else:
             from xaynet_amd.ops.cpu_engine import CpuPlaneAggregator
 
@@ -98,22 +105,28 @@ def _worker_main(rank: int, world: int, device_kind: str, cfg_args, length: int,
         mask_vals = None
 
         def stage_and_aggregate(slot_list):
-            """Pinned-ring slots -> pool rows (async H2D) -> K3; frees slots."""
+            """Ring slots -> pinned rows -> pool rows (async H2D) -> K3; frees slots."""
             nonlocal_free = []
             for start in range(0, len(slot_list), batch):
                 group = slot_list[start : start + batch]
                 if copy_stream is not None:
-                    with torch.cuda.stream(copy_stream):
-                        for i, slot in enumerate(group):
-                            off = slot * sbytes
-                            pool[i, :row_bytes].copy_(
-                                host_t[off : off + row_bytes], non_blocking=True)
-                        copy_done.record(copy_stream)
+                    # the K3 that read the pool last must be done before the
+                    # copy stream writes the pool's rows again
+                    copy_stream.wait_event(agg_done)
+                    for i, slot in enumerate(group):
+                        off = slot * sbytes
+                        row = stage[i % 2]
+                        stage_free[i % 2].synchronize()  # the DMA that last read this row
+                        row.copy_(host_t[off : off + row_bytes])
+                        with torch.cuda.stream(copy_stream):
+                            pool[i, :row_bytes].copy_(row, non_blocking=True)
+                            stage_free[i % 2].record(copy_stream)
+                    copy_done.record(copy_stream)
                     torch.cuda.current_stream().wait_event(copy_done)
+                    # K3 runs async on the compute stream; the slots are
+                    # already read out, so nothing here waits for the DMA
                     eng.aggregate_pool(pool, len(group))
-                    # free slots only once the DMA out of them has finished;
-                    # K3 keeps running async on the compute stream meanwhile
-                    copy_done.synchronize()
+                    agg_done.record()
                 else:
                     for i, slot in enumerate(group):
                         off = slot * sbytes
@@ -162,8 +175,6 @@ def _worker_main(rank: int, world: int, device_kind: str, cfg_args, length: int,
                 break
         if dist is not None:
             dist.destroy_process_group()
-        if device_kind == "cuda":
-            _hip.host_unregister(host.ctypes.data)
         del host_t, host, pool, mask_vals  # release shm buffer exports
         import gc
 
@@ -447,7 +458,7 @@ class MultiGpuServeDriver(threading.Thread):
     def _drain_one(self) -> bool:
         """Pop one staged update into a ring slot; False when none left."""
         # zero-copy: the staged MaskObject's limbs are memcpy'd straight
-        # into the pinned ring slot (one copy, vs serialize -> py bytes
+        # into the ring slot (one copy, vs serialize -> py bytes
         # -> slice -> ring = four copies of a 175 MB update)
         res = self.plane.put_update_direct(
             lambda ptr, cap: self.coordinator.pop_staged_vect(ptr, cap))
