@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Time k3_aggregate variants on MI355X: the generic kernel's EPT values, the
-LDS-staged kernels (201 / 202), the tile-streaming kernel (401 nontemporal,
-402 default loads) and its loader-wave form (411 nontemporal, 412 default).
+tile-streaming kernel (401 nontemporal, 402 default loads) and its loader-wave
+form (411 nontemporal, 412 default).
 
 Usage: python scripts/k3_sweep.py [--length 25000000] [--pool 300] [--bpn 7]
            [--epts 0,4,401,402,411,412] [--ceiling] [--check]

@@ -1,8 +1,8 @@
 """Loader-wave K3 kernel (ept 411 / 412): the host plan, and bit-exact digit
 planes against numpy on the GPU.
 
-The plan tests need no GPU: _hip._k3_loader_plan is the function the launcher
-itself uses, on top of the tile plan of the tile-streaming kernel.
+The plan tests need no GPU: _hip._k3_loader_plan reads the shape table and the
+tile plan that the launcher itself uses.
 """
 from functools import lru_cache
 from types import SimpleNamespace
@@ -80,7 +80,15 @@ def case_lengths(bpn):
     # a remainder; one full group and no remainder block; a full group, a
     # group with one valid tile and the remainder; a group with CONS - 1 valid
     # tiles; remainder only (falls back)
-    return (tile, tile + 1, cons * tile, (cons + 1) * tile + 3, (2 * cons - 1) * tile, 3)
+    lengths = (tile, tile + 1, cons * tile, (cons + 1) * tile + 3, (2 * cons - 1) * tile, 3)
+    # the largest remainder: every round of the remainder block's loop runs
+    # and the last is one element short; and, where the block's 64 * (cons + 1)
+    # threads need a second round for it, a remainder with one element in that
+    # round, whose other threads take the guard
+    lengths += (2 * tile - 1,)
+    if tile + 64 * (cons + 1) + 1 < 2 * tile:
+        lengths += (tile + 64 * (cons + 1) + 1,)
+    return lengths
 
 
 def case_rows(bpn):

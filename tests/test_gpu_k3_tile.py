@@ -84,7 +84,15 @@ def case_lengths(bpn):
     tile, waves = p["tile_elems"], p["waves"]
     # one tile; one tile + 1; a full block, a partial block and a tail;
     # remainder only
-    return (tile, tile + 1, (waves + 1) * tile + 3, 3)
+    lengths = (tile, tile + 1, (waves + 1) * tile + 3, 3)
+    # the largest remainder: every round of the remainder block's loop runs
+    # and the last is one element short; and, where the block's 64 * waves
+    # threads need a second round for it, a remainder with one element in that
+    # round, whose other threads take the guard
+    lengths += (2 * tile - 1,)
+    if tile + 64 * waves + 1 < 2 * tile:
+        lengths += (tile + 64 * waves + 1,)
+    return lengths
 
 
 def case_rows(bpn):

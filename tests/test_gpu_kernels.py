@@ -90,11 +90,11 @@ def test_k3_aggregate_bit_exact_vs_cpu():
 
 
 def test_k3_variants_agree():
-    """All K3 load variants (generic EPT 4/8/16, LDS-staged 201/202) produce
-    identical digit planes, including partial tail tiles."""
+    """All generic K3 load variants (EPT 4/8/16) produce identical digit
+    planes, including partial tail chunks."""
     from xaynet_amd import _hip
 
-    length = 5000  # not a multiple of the 2048/4096 LDS tiles
+    length = 5000
     eng, c = make_engine(length, (1, 0, 0, 6))  # bpn=7
     rng = np.random.default_rng(9)
     n = 6
@@ -105,14 +105,14 @@ def test_k3_variants_agree():
     torch.cuda.synchronize()
 
     planes = {}
-    for ept in (4, 8, 16, 201, 202):
+    for ept in (4, 8, 16):
         eng.reset()
         _hip.aggregate_batch(
             eng.acc.data_ptr(), pool.data_ptr(), pool.stride(0), n, length, eng.bpn, ept
         )
         torch.cuda.synchronize()
         planes[ept] = eng.acc.cpu().numpy().copy()
-    for ept in (8, 16, 201, 202):
+    for ept in (8, 16):
         assert (planes[ept] == planes[4]).all(), f"variant ept={ept} diverges"
 
 
@@ -146,8 +146,7 @@ def test_k3_wide_variants_agree():
 # ---------------------------------------------- K3: every instantiation
 #
 # bytes per number -> (default, alternate, alternate) elements per thread, the
-# K3_CASE lines of xhip_k3_aggregate; bpn <= 8 also has the LDS-staged kernels
-# (ept 201 / 202: 2048- / 4096-element tiles).
+# K3_CASE lines of xhip_k3_aggregate.
 K3_EPTS = {
     1: (16, 32, 16), 2: (8, 16, 8), 3: (16, 16, 16), 4: (4, 8, 16), 5: (16, 16, 16),
     6: (8, 8, 8), 7: (4, 8, 16), 8: (4, 2, 8), 9: (4, 4, 4), 10: (2, 4, 8), 11: (4, 4, 4),
@@ -155,14 +154,14 @@ K3_EPTS = {
     18: (2, 2, 2), 37: (4, 4, 4), 38: (2, 2, 2), 39: (4, 4, 4), 40: (2, 1, 2),
 }
 K3_ROWS = 5
-# 4099: a full 4096-tile (two 2048-tiles) plus 3; 3: shorter than every EPT
+# 4099: full chunks at every EPT plus 3; 3: shorter than every EPT
 K3_LENGTHS = (4099, 3, 1)
 
 
 def k3_variants(bpn):
     """Every distinct kernel the launcher can pick for bpn: 0 is the default."""
     default, *alts = K3_EPTS[bpn]
-    return [0] + sorted(set(alts) - {default}) + ([201, 202] if bpn <= 8 else [])
+    return [0] + sorted(set(alts) - {default})
 
 
 def k3_row_stride(length, bpn):
@@ -223,7 +222,7 @@ def k3_run(flat, lead, stride, prior, length, bpn, ept):
 
 @pytest.mark.parametrize("bpn", sorted(K3_EPTS))
 def test_k3_every_variant_vs_numpy(bpn):
-    """Each K3 instantiation (every EPT of every bpn, and the LDS kernels)
+    """Each K3 instantiation the K3_CASE lines select (every EPT of every bpn)
     adds exactly the byte-gathered digits into a pre-filled accumulator, at a
     full tile plus a tail and at lengths shorter than one thread's share; the
     CPU plane agrees with the numpy reference where a config has that bpn."""
@@ -246,15 +245,6 @@ def test_k3_every_variant_vs_numpy(bpn):
             bad = np.argwhere(got != expect)
             assert bad.size == 0, (f"bpn {bpn} ept {ept} n {length}: {len(bad)} wrong, first "
                                    f"(digit, element) {bad[:4].tolist()}")
-
-
-def test_k3_lds_request_on_misaligned_pool():
-    """ept=201 on a pool whose base is 4 bytes past a 16-byte boundary: the
-    launcher falls back to the generic kernel, with the same result."""
-    bpn, length, lead = 7, 4099, 4
-    flat, pool, prior, expect = k3_inputs(bpn, length, lead)
-    got = k3_run(flat, lead, pool.shape[1], prior, length, bpn, 201)
-    assert (got == expect).all()
 
 
 def test_k4_full_roundtrip_vs_oracle():

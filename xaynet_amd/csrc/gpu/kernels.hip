@@ -432,77 +432,120 @@ __global__ void k3_aggregate(
     }
 }
 
-// K3 LDS-staged variant: the whole workgroup stages a contiguous
-// (E elements x BPN bytes) row tile through LDS with perfectly coalesced
-// vector loads, then each thread accumulates E/TPB *strided* elements out of
-// LDS (lane-stride BPN bytes -> conflict-light). This trades the generic
-// kernel's 28-line-per-instruction scatter loads for 4-line coalesced ones.
-// Requires 16B-aligned update rows (launcher falls back otherwise).
-template <int BPN, int E>
-__global__ void k3_aggregate_lds(
-    uint64_t* __restrict__ acc, const uint8_t* __restrict__ updates,
-    uint64_t stride, uint32_t n_updates, uint64_t len) {
-    constexpr int TPB = 256;
-    constexpr int EPT = E / TPB;             // elements per thread (strided by TPB)
-    constexpr int NDIG = (BPN + 3) / 4;
-    constexpr int TILE_BYTES = E * BPN;
-    constexpr int NVEC = TILE_BYTES / 8;     // uint2 (8 B) staging loads
-    static_assert(TILE_BYTES % (8 * TPB) == 0, "tile must stage as whole uint2 rounds");
-    __shared__ uint32_t lds[TILE_BYTES / 4 + 1];  // +1: cross-word gather at the tile edge
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-    const uint64_t tile0 = uint64_t(blockIdx.x) * E;
-    if (tile0 >= len) return;
-    const int t = threadIdx.x;
-    const int nelem_tile = (tile0 + E <= len) ? E : int(len - tile0);
-    const int valid_vec = (int(uint64_t(nelem_tile) * BPN) + 7) / 8;  // uint2s to stage
+// ---- K3, tiled kernels: the pieces k3_aggregate_tile and k3_aggregate_loader
+// share. A tile is 64*T consecutive elements of BPN bytes; lane l owns elements
+// l + 64k of it. The ring control, which is where the two kernels differ, is
+// theirs.
+template <int BPN, int T>
+struct K3Tile {
+    static constexpr int NDIG = (BPN + 3) / 4;
+    static constexpr int NW = (BPN + 6) / 4;  // words an element can straddle
+    static constexpr int TILE_BYTES = 64 * T * BPN;
+    static constexpr int PIECES = TILE_BYTES / 1024;
+    // +4 words: the word after an element's last may be read (and masked off)
+    static constexpr int SLOT_WORDS = TILE_BYTES / 4 + 4;
+    static_assert(TILE_BYTES % 1024 == 0, "a tile is whole 1-KiB pieces");
+};
 
-    uint64_t racc[EPT][NDIG];
+// The digits of the element that starts sh bytes (0..3, known at run time
+// only) into w[0], added to a[].
+template <int BPN, int NW, int NDIG>
+__device__ __forceinline__ void k3_add_digits(const uint32_t (&w)[NW], uint32_t sh,
+                                              uint64_t (&a)[NDIG]) {
 #pragma unroll
-    for (int e = 0; e < EPT; ++e)
-#pragma unroll
-        for (int d = 0; d < NDIG; ++d) racc[e][d] = 0;
-
-    for (uint32_t u = 0; u < n_updates; ++u) {
-        const uint8_t* row = updates + u * stride + tile0 * uint64_t(BPN);
-        __syncthreads();  // previous iteration's reads done before overwrite
-        const uint64_t* src = reinterpret_cast<const uint64_t*>(row);
-#pragma unroll
-        for (int i = 0; i < NVEC / TPB; ++i) {
-            int v = t + i * TPB;
-            if (v < valid_vec) {
-                uint64_t x = __builtin_nontemporal_load(&src[v]);
-                lds[2 * v] = uint32_t(x);
-                lds[2 * v + 1] = uint32_t(x >> 32);
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < EPT; ++k) {
-            int e = t + k * TPB;  // element within tile
-#pragma unroll
-            for (int d = 0; d < NDIG; ++d) {
-                int byte0 = e * BPN + 4 * d;
-                int nb = (BPN - 4 * d) >= 4 ? 4 : (BPN - 4 * d);
-                int wi = byte0 >> 2, sh = (byte0 & 3) * 8;
-                uint32_t lo = lds[wi] >> sh;
-                uint32_t hi = sh ? (lds[wi + 1] << (32 - sh)) : 0;
-                uint32_t val = lo | hi;
-                if (nb < 4) val &= (1u << (8 * nb)) - 1;
-                racc[k][d] += uint64_t(val);
-            }
-        }
+    for (int d = 0; d < NDIG; ++d) {
+        const int nb = (BPN - 4 * d) >= 4 ? 4 : (BPN - 4 * d);
+        uint32_t val = __builtin_amdgcn_alignbyte(d + 1 < NW ? w[d + 1] : 0u, w[d], sh);
+        if (nb < 4) val &= (1u << (8 * nb)) - 1;
+        a[d] += uint64_t(val);
     }
-
-#pragma unroll
-    for (int d = 0; d < NDIG; ++d)
-#pragma unroll
-        for (int k = 0; k < EPT; ++k) {
-            int e = t + k * TPB;
-            if (e < nelem_tile) acc[uint64_t(d) * len + tile0 + e] += racc[k][d];
-        }
 }
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+// The remainder block: elements [rem_start, len), fewer than one tile. Thread
+// t of the NWAVES waves sums elements rem_start + t + k*64*NWAVES over all rows
+// with plain dword loads (rows are 16B-aligned and padded past their last
+// element). A launch of its own would cost n_updates load latencies in series
+// after the tiles are done; here they run beside the tile blocks.
+template <int BPN, int T, int NWAVES>
+__device__ __forceinline__ void k3_remainder(uint64_t* __restrict__ acc,
+                                             const uint8_t* __restrict__ updates,
+                                             uint64_t stride, uint32_t n_updates, uint64_t len,
+                                             uint64_t rem_start) {
+    constexpr int NDIG = K3Tile<BPN, T>::NDIG, NW = K3Tile<BPN, T>::NW;
+    constexpr int KR = (T + NWAVES - 1) / NWAVES;
+    uint64_t rr[KR][NDIG];
+#pragma unroll
+    for (int k = 0; k < KR; ++k)
+#pragma unroll
+        for (int d = 0; d < NDIG; ++d) rr[k][d] = 0;
+    const uint64_t b0 = (rem_start + threadIdx.x) * BPN;  // + k*64*NWAVES*BPN: same shift
+    const uint32_t sh = uint32_t(b0) & 3;
+    for (uint32_t u = 0; u < n_updates; ++u) {
+        const uint32_t* r =
+            reinterpret_cast<const uint32_t*>(updates + uint64_t(u) * stride) + (b0 >> 2);
+#pragma unroll
+        for (int k = 0; k < KR; ++k) {
+            if (rem_start + threadIdx.x + k * (64 * NWAVES) >= len) continue;
+            uint32_t w[NW];
+#pragma unroll
+            for (int j = 0; j < NW; ++j) w[j] = r[k * (16 * NWAVES * BPN) + j];
+            k3_add_digits<BPN>(w, sh, rr[k]);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < KR; ++k) {
+        const uint64_t e = rem_start + threadIdx.x + k * (64 * NWAVES);
+        if (e >= len) continue;
+#pragma unroll
+        for (int d = 0; d < NDIG; ++d) acc[uint64_t(d) * len + e] += rr[k][d];
+    }
+}
+
+// One tile's PIECES LDS-DMA loads: TILE_BYTES from g (this lane's 16 bytes of
+// the first piece) into the slot at l. AUX is the cache policy.
+template <int BPN, int T, int AUX>
+__device__ __forceinline__ void k3_issue_tile(const uint8_t* g, uint32_t* l) {
+    static_assert(AUX == 0 || AUX == 2, "default or nontemporal");
+#pragma unroll
+    for (int p = 0; p < K3Tile<BPN, T>::PIECES; ++p) {
+        auto gp = (const __attribute__((address_space(1))) void*)(g + p * 1024);
+        auto lp = (__attribute__((address_space(3))) void*)(l + p * 256);
+        // the policy must be a literal constant
+        if constexpr (AUX == 0)
+            __builtin_amdgcn_global_load_lds(gp, lp, 16, 0, 0);
+        else
+            __builtin_amdgcn_global_load_lds(gp, lp, 16, 0, 2);
+    }
+}
+
+// One row of a tile out of its slot: r is the slot plus this lane's rword.
+// Element l + 64k starts at byte l*BPN + 64k*BPN of the tile, so the shift rsh
+// inside its first word is the same for every k.
+template <int BPN, int T>
+__device__ __forceinline__ void k3_consume_tile(const uint32_t* r, uint32_t rsh,
+                                                uint64_t (&racc)[T][K3Tile<BPN, T>::NDIG]) {
+    constexpr int NW = K3Tile<BPN, T>::NW;
+#pragma unroll
+    for (int k = 0; k < T; ++k) {
+        uint32_t w[NW];
+#pragma unroll
+        for (int j = 0; j < NW; ++j) w[j] = r[k * 16 * BPN + j];
+        k3_add_digits<BPN>(w, rsh, racc[k]);
+    }
+}
+
+// A tile's sums into the planes; e0 is the lane's first element. Coalesced.
+template <int BPN, int T>
+__device__ __forceinline__ void k3_flush_tile(uint64_t* __restrict__ acc, uint64_t len,
+                                              uint64_t e0,
+                                              const uint64_t (&racc)[T][K3Tile<BPN, T>::NDIG]) {
+#pragma unroll
+    for (int d = 0; d < K3Tile<BPN, T>::NDIG; ++d)
+#pragma unroll
+        for (int k = 0; k < T; ++k) acc[uint64_t(d) * len + e0 + 64 * k] += racc[k][d];
+}
 
 // K3 tile-streaming variant: a wave owns a tile of 64*T consecutive elements
 // and streams its TILE_BYTES of every update row through a wave-private ring
@@ -522,59 +565,16 @@ template <int BPN, int T, int D, int WAVES, int AUX>
 __global__ __launch_bounds__(WAVES * 64) void k3_aggregate_tile(
     uint64_t* __restrict__ acc, const uint8_t* __restrict__ updates, uint64_t stride,
     uint32_t n_updates, uint64_t len, uint32_t n_tiles) {
-    constexpr int NDIG = (BPN + 3) / 4;
-    constexpr int NW = (BPN + 6) / 4;  // words an element can straddle
-    constexpr int TILE_BYTES = 64 * T * BPN;
-    constexpr int PIECES = TILE_BYTES / 1024;
-    // +4 words: the word after an element's last may be read (and masked off)
-    constexpr int SLOT_WORDS = TILE_BYTES / 4 + 4;
-    static_assert(TILE_BYTES % 1024 == 0, "a tile is whole 1-KiB pieces");
+    using Tile = K3Tile<BPN, T>;
+    constexpr int NDIG = Tile::NDIG, TILE_BYTES = Tile::TILE_BYTES, PIECES = Tile::PIECES,
+                  SLOT_WORDS = Tile::SLOT_WORDS;
     static_assert(D >= 2 && PIECES * (D - 1) <= 63, "vmcnt is a 6-bit count");
-    static_assert(AUX == 0 || AUX == 2, "default or nontemporal");
     __shared__ __attribute__((aligned(16))) uint32_t ring[WAVES * D * SLOT_WORDS];
 
     const uint64_t rem_start = uint64_t(n_tiles) * (64 * T);
     const bool has_rem = rem_start < len;  // then block 0 is the remainder block
     if (has_rem && blockIdx.x == 0) {
-        // Elements [rem_start, len), fewer than one tile: thread t sums
-        // elements rem_start + t + k*blockDim over all rows with plain dword
-        // loads (rows are 16B-aligned and padded past their last element). A
-        // launch of its own would cost n_updates load latencies in series after
-        // the tiles are done; here they run beside the tile blocks.
-        constexpr int KR = (T + WAVES - 1) / WAVES;
-        uint64_t rr[KR][NDIG];
-#pragma unroll
-        for (int k = 0; k < KR; ++k)
-#pragma unroll
-            for (int d = 0; d < NDIG; ++d) rr[k][d] = 0;
-        const uint64_t b0 = (rem_start + threadIdx.x) * BPN;  // + k*64*WAVES*BPN: same shift
-        const uint32_t sh = uint32_t(b0) & 3;
-        for (uint32_t u = 0; u < n_updates; ++u) {
-            const uint32_t* r =
-                reinterpret_cast<const uint32_t*>(updates + uint64_t(u) * stride) + (b0 >> 2);
-#pragma unroll
-            for (int k = 0; k < KR; ++k) {
-                if (rem_start + threadIdx.x + k * (64 * WAVES) >= len) continue;
-                uint32_t w[NW];
-#pragma unroll
-                for (int j = 0; j < NW; ++j) w[j] = r[k * (16 * WAVES * BPN) + j];
-#pragma unroll
-                for (int d = 0; d < NDIG; ++d) {
-                    const int nb = (BPN - 4 * d) >= 4 ? 4 : (BPN - 4 * d);
-                    uint32_t val =
-                        __builtin_amdgcn_alignbyte(d + 1 < NW ? w[d + 1] : 0u, w[d], sh);
-                    if (nb < 4) val &= (1u << (8 * nb)) - 1;
-                    rr[k][d] += uint64_t(val);
-                }
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < KR; ++k) {
-            const uint64_t e = rem_start + threadIdx.x + k * (64 * WAVES);
-            if (e >= len) continue;
-#pragma unroll
-            for (int d = 0; d < NDIG; ++d) acc[uint64_t(d) * len + e] += rr[k][d];
-        }
+        k3_remainder<BPN, T, WAVES>(acc, updates, stride, n_updates, len, rem_start);
         return;
     }
 
@@ -596,34 +596,10 @@ __global__ __launch_bounds__(WAVES * 64) void k3_aggregate_tile(
         for (int d = 0; d < NDIG; ++d) racc[k][d] = 0;
 
     auto issue = [&](uint32_t u, uint32_t slot) {
-        const uint8_t* g = src + uint64_t(u) * stride;
-        uint32_t* l = wring + slot * SLOT_WORDS;
-#pragma unroll
-        for (int p = 0; p < PIECES; ++p) {
-            auto gp = (const __attribute__((address_space(1))) void*)(g + p * 1024);
-            auto lp = (__attribute__((address_space(3))) void*)(l + p * 256);
-            // the policy must be a literal constant
-            if constexpr (AUX == 0)
-                __builtin_amdgcn_global_load_lds(gp, lp, 16, 0, 0);
-            else
-                __builtin_amdgcn_global_load_lds(gp, lp, 16, 0, 2);
-        }
+        k3_issue_tile<BPN, T, AUX>(src + uint64_t(u) * stride, wring + slot * SLOT_WORDS);
     };
     auto consume = [&](uint32_t slot) {
-        const uint32_t* r = wring + slot * SLOT_WORDS + rword;
-#pragma unroll
-        for (int k = 0; k < T; ++k) {
-            uint32_t w[NW];
-#pragma unroll
-            for (int j = 0; j < NW; ++j) w[j] = r[k * 16 * BPN + j];
-#pragma unroll
-            for (int d = 0; d < NDIG; ++d) {
-                const int nb = (BPN - 4 * d) >= 4 ? 4 : (BPN - 4 * d);
-                uint32_t val = __builtin_amdgcn_alignbyte(d + 1 < NW ? w[d + 1] : 0u, w[d], rsh);
-                if (nb < 4) val &= (1u << (8 * nb)) - 1;
-                racc[k][d] += uint64_t(val);
-            }
-        }
+        k3_consume_tile<BPN, T>(wring + slot * SLOT_WORDS + rword, rsh, racc);
     };
     auto next = [](uint32_t slot) { return slot + 1 == D ? 0u : slot + 1; };
 
@@ -647,17 +623,13 @@ __global__ __launch_bounds__(WAVES * 64) void k3_aggregate_tile(
         rslot = next(rslot);
     }
 
-    const uint64_t e0 = uint64_t(tile) * (64 * T) + lane;
-#pragma unroll
-    for (int d = 0; d < NDIG; ++d)
-#pragma unroll
-        for (int k = 0; k < T; ++k) acc[uint64_t(d) * len + e0 + 64 * k] += racc[k][d];
+    k3_flush_tile<BPN, T>(acc, len, uint64_t(tile) * (64 * T) + lane, racc);
 }
 
-// K3 loader-wave variant of the tile kernel: the same tiles, the same consume
-// arithmetic and the same flush, but the LDS-DMA loads of a block all come
-// from one wave. A block is 1 + CONS waves over a group of CONS adjacent
-// tiles. Wave 0, the loader, holds no accumulators and reads no LDS: for every
+// K3 loader-wave variant of the tile kernel: the same tiles and the same
+// shared pieces (remainder, issue, consume, flush), but the LDS-DMA loads of a
+// block all come from one wave. A block is 1 + CONS waves over a group of CONS
+// adjacent tiles. Wave 0, the loader, holds no accumulators and reads no LDS: for every
 // row it issues the PB = CONS * PIECES loads of the group (CONS * TILE_BYTES
 // contiguous bytes) into one of D ring slots. Waves 1..CONS are consumers;
 // consumer c owns tile group * CONS + c - 1 and reads its part of the slot.
@@ -677,57 +649,18 @@ template <int BPN, int T, int D, int CONS, int AUX>
 __global__ __launch_bounds__((1 + CONS) * 64) void k3_aggregate_loader(
     uint64_t* __restrict__ acc, const uint8_t* __restrict__ updates, uint64_t stride,
     uint32_t n_updates, uint64_t len, uint32_t n_tiles) {
-    constexpr int NDIG = (BPN + 3) / 4;
-    constexpr int NW = (BPN + 6) / 4;  // words an element can straddle
-    constexpr int NWAVES = 1 + CONS;
-    constexpr int TILE_BYTES = 64 * T * BPN;
-    constexpr int PIECES = TILE_BYTES / 1024;
+    using Tile = K3Tile<BPN, T>;
+    constexpr int NDIG = Tile::NDIG, TILE_BYTES = Tile::TILE_BYTES, PIECES = Tile::PIECES,
+                  SLOT_WORDS = Tile::SLOT_WORDS;
     constexpr int PB = CONS * PIECES;  // loads per row, all from the loader
-    // +4 words: the word after an element's last may be read (and masked off)
-    constexpr int SLOT_WORDS = TILE_BYTES / 4 + 4;
-    static_assert(TILE_BYTES % 1024 == 0, "a tile is whole 1-KiB pieces");
     static_assert(D >= 2 && PB * (D - 2) <= 63, "vmcnt is a 6-bit count");
-    static_assert(AUX == 0 || AUX == 2, "default or nontemporal");
     __shared__ __attribute__((aligned(16))) uint32_t ring[D * CONS * SLOT_WORDS];
 
     const uint64_t rem_start = uint64_t(n_tiles) * (64 * T);
     const bool has_rem = rem_start < len;  // then block 0 is the remainder block
     if (has_rem && blockIdx.x == 0) {
-        // as in k3_aggregate_tile; the whole block leaves before any barrier
-        constexpr int KR = (T + NWAVES - 1) / NWAVES;
-        uint64_t rr[KR][NDIG];
-#pragma unroll
-        for (int k = 0; k < KR; ++k)
-#pragma unroll
-            for (int d = 0; d < NDIG; ++d) rr[k][d] = 0;
-        const uint64_t b0 = (rem_start + threadIdx.x) * BPN;  // + k*64*NWAVES*BPN: same shift
-        const uint32_t sh = uint32_t(b0) & 3;
-        for (uint32_t u = 0; u < n_updates; ++u) {
-            const uint32_t* r =
-                reinterpret_cast<const uint32_t*>(updates + uint64_t(u) * stride) + (b0 >> 2);
-#pragma unroll
-            for (int k = 0; k < KR; ++k) {
-                if (rem_start + threadIdx.x + k * (64 * NWAVES) >= len) continue;
-                uint32_t w[NW];
-#pragma unroll
-                for (int j = 0; j < NW; ++j) w[j] = r[k * (16 * NWAVES * BPN) + j];
-#pragma unroll
-                for (int d = 0; d < NDIG; ++d) {
-                    const int nb = (BPN - 4 * d) >= 4 ? 4 : (BPN - 4 * d);
-                    uint32_t val =
-                        __builtin_amdgcn_alignbyte(d + 1 < NW ? w[d + 1] : 0u, w[d], sh);
-                    if (nb < 4) val &= (1u << (8 * nb)) - 1;
-                    rr[k][d] += uint64_t(val);
-                }
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < KR; ++k) {
-            const uint64_t e = rem_start + threadIdx.x + k * (64 * NWAVES);
-            if (e >= len) continue;
-#pragma unroll
-            for (int d = 0; d < NDIG; ++d) acc[uint64_t(d) * len + e] += rr[k][d];
-        }
+        // the whole block leaves before any barrier
+        k3_remainder<BPN, T, 1 + CONS>(acc, updates, stride, n_updates, len, rem_start);
         return;
     }
 
@@ -747,20 +680,8 @@ __global__ __launch_bounds__((1 + CONS) * 64) void k3_aggregate_loader(
         auto issue = [&](uint32_t u, uint32_t slot) {
             uint32_t* l = ring + slot * (CONS * SLOT_WORDS);
 #pragma unroll
-            for (int c = 0; c < CONS; ++c) {
-                const uint8_t* g = src[c] + uint64_t(u) * stride;
-#pragma unroll
-                for (int p = 0; p < PIECES; ++p) {
-                    auto gp = (const __attribute__((address_space(1))) void*)(g + p * 1024);
-                    auto lp =
-                        (__attribute__((address_space(3))) void*)(l + c * SLOT_WORDS + p * 256);
-                    // the policy must be a literal constant
-                    if constexpr (AUX == 0)
-                        __builtin_amdgcn_global_load_lds(gp, lp, 16, 0, 0);
-                    else
-                        __builtin_amdgcn_global_load_lds(gp, lp, 16, 0, 2);
-                }
-            }
+            for (int c = 0; c < CONS; ++c)
+                k3_issue_tile<BPN, T, AUX>(src[c] + uint64_t(u) * stride, l + c * SLOT_WORDS);
         };
         uint32_t wslot = 0, k = 0;
         for (; k < n_updates && k < D - 1; ++k) {  // prologue: rows 0..D-2
@@ -798,20 +719,7 @@ __global__ __launch_bounds__((1 + CONS) * 64) void k3_aggregate_loader(
         for (int d = 0; d < NDIG; ++d) racc[k][d] = 0;
 
     auto consume = [&](uint32_t slot) {
-        const uint32_t* r = cring + slot * (CONS * SLOT_WORDS);
-#pragma unroll
-        for (int k = 0; k < T; ++k) {
-            uint32_t w[NW];
-#pragma unroll
-            for (int j = 0; j < NW; ++j) w[j] = r[k * 16 * BPN + j];
-#pragma unroll
-            for (int d = 0; d < NDIG; ++d) {
-                const int nb = (BPN - 4 * d) >= 4 ? 4 : (BPN - 4 * d);
-                uint32_t val = __builtin_amdgcn_alignbyte(d + 1 < NW ? w[d + 1] : 0u, w[d], rsh);
-                if (nb < 4) val &= (1u << (8 * nb)) - 1;
-                racc[k][d] += uint64_t(val);
-            }
-        }
+        k3_consume_tile<BPN, T>(cring + slot * (CONS * SLOT_WORDS), rsh, racc);
     };
 
     uint32_t rslot = 0;
@@ -825,11 +733,7 @@ __global__ __launch_bounds__((1 + CONS) * 64) void k3_aggregate_loader(
     }
     if (!live) return;
 
-    const uint64_t e0 = uint64_t(tile) * (64 * T) + lane;
-#pragma unroll
-    for (int d = 0; d < NDIG; ++d)
-#pragma unroll
-        for (int k = 0; k < T; ++k) acc[uint64_t(d) * len + e0 + 64 * k] += racc[k][d];
+    k3_flush_tile<BPN, T>(acc, len, uint64_t(tile) * (64 * T) + lane, racc);
 }
 
 // Read-only ceiling probe for K3 sweeps: every lane reads 16 bytes per load,
@@ -2005,61 +1909,86 @@ hipError_t xhip_k1_expand_batch(const uint32_t* keys_dev, const uint64_t* start_
 
 // ---- K3 ----
 
-// The tile kernel's shape per bytes-per-number: X(BPN, T, D, WAVES). T is the
-// smallest value >= 4 with T*BPN % 16 == 0 (whole 1-KiB pieces per tile); D
-// and WAVES are the measured choice (profiles/r10_k3_tile.md). A bpn without
-// a line has no tile kernel. It is the default of no bpn any more: bpn 7 runs
-// the loader-wave kernel below (profiles/r12_k3_loader.md), the others the
-// generic kernel; codes 401 / 402 still select it.
+// T of the tiled kernels: the smallest value >= 4 with T*bpn % 16 == 0, so that
+// a tile of 64*T elements is whole 1-KiB pieces.
+constexpr int k3_tile_t(int bpn) {
+    int t = 4;
+    while (t * bpn % 16 != 0) ++t;
+    return t;
+}
+
+// The tile kernel's measured shape per bytes-per-number: X(BPN, D, WAVES)
+// (profiles/r10_k3_tile.md). A bpn without a line has no tile kernel. It is
+// the default of no bpn any more: bpn 7 runs the loader-wave kernel below
+// (profiles/r12_k3_loader.md), the others the generic kernel; codes 401 / 402
+// still select it.
 #define K3_TILE_CONFIGS(X)                                                                      \
-    X(3, 16, 3, 4)                                                                              \
-    X(7, 16, 3, 4)                                                                              \
-    X(10, 8, 3, 4)                                                                              \
-    X(18, 8, 2, 4)                                                                              \
-    X(40, 4, 2, 4)
+    X(3, 3, 4)                                                                                  \
+    X(7, 3, 4)                                                                                  \
+    X(10, 3, 4)                                                                                 \
+    X(18, 2, 4)                                                                                 \
+    X(40, 2, 4)
+
+// The loader-wave kernel's shape per bytes-per-number: X(BPN, D, CONS). One
+// wave tracks at most 64 loads, so CONS * pieces * (D - 2) <= 63: bpn 18 and 40
+// have no loader kernel. bpn 7 is the measured choice (eight tiles, 56 KiB
+// contiguous per row and block, two slots: profiles/r12_k3_loader.md); bpn 3
+// and 10 have no benchmark and keep the tile kernel's depth and tiles per block.
+#define K3_LOADER_CONFIGS(X)                                                                    \
+    X(3, 3, 4)                                                                                  \
+    X(7, 2, 8)                                                                                  \
+    X(10, 3, 4)
+
+// Both tiled kernels take the same arguments; what a launch and the plans need
+// to know of one: its two cache policies, the ring depth, the tiles a block
+// covers and the waves of a block. All zero where bpn has no such kernel.
+using K3TiledKernel = void (*)(uint64_t*, const uint8_t*, uint64_t, uint32_t, uint64_t, uint32_t);
+struct K3TiledShape {
+    K3TiledKernel nontemporal, cached;
+    uint32_t depth, tiles_per_block, waves;
+};
+
+static K3TiledShape k3_tiled_shape(int bpn, bool loader) {
+#define K3_TILE_ROW(BPN, D, WAVES)                                                              \
+    if (!loader && bpn == BPN)                                                                  \
+        return {k3_aggregate_tile<BPN, k3_tile_t(BPN), D, WAVES, 2>,                            \
+                k3_aggregate_tile<BPN, k3_tile_t(BPN), D, WAVES, 0>, D, WAVES, WAVES};
+    K3_TILE_CONFIGS(K3_TILE_ROW)
+#undef K3_TILE_ROW
+#define K3_LOADER_ROW(BPN, D, CONS)                                                             \
+    if (loader && bpn == BPN)                                                                   \
+        return {k3_aggregate_loader<BPN, k3_tile_t(BPN), D, CONS, 2>,                           \
+                k3_aggregate_loader<BPN, k3_tile_t(BPN), D, CONS, 0>, D, CONS, 1 + CONS};
+    K3_LOADER_CONFIGS(K3_LOADER_ROW)
+#undef K3_LOADER_ROW
+    return {nullptr, nullptr, 0, 0, 0};
+}
 
 void xhip_k3_tile_plan(uint64_t len, int bpn, uint64_t stride, XhipK3TilePlan* plan) {
     *plan = XhipK3TilePlan{0, 0, 0, 0, 0, -1};
-    uint32_t t = 0, d = 0, waves = 0;
-#define K3_TILE_ROW(BPN, T, D, WAVES)                                                           \
-    if (bpn == BPN) t = T, d = D, waves = WAVES;
-    K3_TILE_CONFIGS(K3_TILE_ROW)
-#undef K3_TILE_ROW
+    const K3TiledShape tile = k3_tiled_shape(bpn, false);
     // rows keep every 16-byte load aligned, and hold len elements plus the 16
     // bytes of padding the remainder block's last word may reach into
-    if (t == 0 || stride % 16 != 0 || stride < 16 || len > (stride - 16) / uint64_t(bpn)) return;
-    plan->tile_elems = 64 * t;
-    plan->depth = d;
-    plan->waves = waves;
+    if (tile.waves == 0 || stride % 16 != 0 || stride < 16 ||
+        len > (stride - 16) / uint64_t(bpn))
+        return;
+    plan->tile_elems = 64 * k3_tile_t(bpn);
+    plan->depth = tile.depth;
+    plan->waves = tile.waves;
     plan->n_tiles = std::min<uint64_t>(len / plan->tile_elems, 0x7fffffffu);
     plan->rem_start = plan->n_tiles * plan->tile_elems;
     if (plan->n_tiles) plan->max_byte = int64_t(plan->rem_start * uint64_t(bpn)) - 1;
 }
 
-// The loader-wave kernel's shape per bytes-per-number: X(BPN, T, D, CONS), T
-// as above. One wave tracks at most 64 loads, so CONS * pieces * (D - 2) <= 63:
-// bpn 18 and 40 have no loader kernel. bpn 7 is the measured choice (eight
-// tiles, 56 KiB contiguous per row and block, two slots:
-// profiles/r12_k3_loader.md); bpn 3 and 10 have no benchmark and keep the tile
-// kernel's depth and tiles per block.
-#define K3_LOADER_CONFIGS(X)                                                                    \
-    X(3, 16, 3, 4)                                                                              \
-    X(7, 16, 2, 8)                                                                              \
-    X(10, 8, 3, 4)
-
 void xhip_k3_loader_plan(uint64_t len, int bpn, uint64_t stride, XhipK3LoaderPlan* plan) {
     *plan = XhipK3LoaderPlan{0, 0, 0, 0, 0, 0, -1};
-    uint32_t d = 0, cons = 0;
-#define K3_LOADER_ROW(BPN, T, D, CONS)                                                          \
-    if (bpn == BPN) d = D, cons = CONS;
-    K3_LOADER_CONFIGS(K3_LOADER_ROW)
-#undef K3_LOADER_ROW
+    const K3TiledShape loader = k3_tiled_shape(bpn, true);
     XhipK3TilePlan tiles;
     xhip_k3_tile_plan(len, bpn, stride, &tiles);
-    if (cons == 0 || tiles.n_tiles == 0) return;
-    plan->consumers = cons;
-    plan->depth = d;
-    plan->tile_blocks = ceil_div_u32(tiles.n_tiles, cons);
+    if (loader.waves == 0 || tiles.n_tiles == 0) return;
+    plan->consumers = loader.tiles_per_block;
+    plan->depth = loader.depth;
+    plan->tile_blocks = ceil_div_u32(tiles.n_tiles, loader.tiles_per_block);
     plan->has_remainder = tiles.rem_start < len ? 1 : 0;
     plan->n_tiles = tiles.n_tiles;
     plan->rem_start = tiles.rem_start;
@@ -2074,57 +2003,23 @@ hipError_t xhip_k3_aggregate(uint64_t* acc, const uint8_t* updates, uint64_t str
     // (profiles/r12_k3_loader.md) as that had beaten the generic kernel
     // (profiles/r10_k3_tile.md). Every other bpn: the generic kernel.
     if (ept <= 0 && bpn == 7) ept = 411;
-    // ept=401/402: tile-streaming kernel (nontemporal / default loads) where
-    // the row has a full tile; needs 16B-aligned rows
-    if (ept == 401 || ept == 402) {
+    // ept=401/402: the tile-streaming kernel, 411/412: its loader-wave form;
+    // the odd code loads nontemporal, the even one with the default policy
+    if (ept == 401 || ept == 402 || ept == 411 || ept == 412) {
+        const K3TiledShape k = k3_tiled_shape(bpn, ept >= 411);
         XhipK3TilePlan plan;
         xhip_k3_tile_plan(len, bpn, stride, &plan);
-        if (plan.n_tiles && reinterpret_cast<uintptr_t>(updates) % 16 == 0) {
+        if (k.waves && plan.n_tiles && reinterpret_cast<uintptr_t>(updates) % 16 == 0) {
             // one block more for the elements past the last full tile
-            const uint64_t blocks_extra = plan.rem_start < len ? 1 : 0;
-#define K3_TILE_CASE(BPN, T, D, WAVES)                                                          \
-    case BPN: {                                                                                 \
-        dim3 grid(ceil_div_u32(plan.n_tiles, WAVES) + blocks_extra), block(WAVES * 64);         \
-        if (ept == 401)                                                                         \
-            hipLaunchKernelGGL((k3_aggregate_tile<BPN, T, D, WAVES, 2>), grid, block, 0, 0,     \
-                               acc, updates, stride, n_updates, len, uint32_t(plan.n_tiles));   \
-        else                                                                                    \
-            hipLaunchKernelGGL((k3_aggregate_tile<BPN, T, D, WAVES, 0>), grid, block, 0, 0,     \
-                               acc, updates, stride, n_updates, len, uint32_t(plan.n_tiles));   \
-        return hipGetLastError();                                                               \
-    }
-            switch (bpn) {
-                K3_TILE_CONFIGS(K3_TILE_CASE)
-                default:;
-            }
-#undef K3_TILE_CASE
+            dim3 grid(ceil_div_u32(plan.n_tiles, k.tiles_per_block) +
+                      (plan.rem_start < len ? 1 : 0));
+            hipLaunchKernelGGL(ept % 2 ? k.nontemporal : k.cached, grid, dim3(k.waves * 64), 0, 0,
+                               acc, updates, stride, n_updates, len, uint32_t(plan.n_tiles));
+            return hipGetLastError();
         }
-        ept = 0;  // no full tile, no tile kernel or misaligned rows: generic kernel
-    }
-    // ept=411/412: the loader-wave form of the tile kernel (nontemporal /
-    // default loads), same fall-backs
-    if (ept == 411 || ept == 412) {
-        XhipK3LoaderPlan lp;
-        xhip_k3_loader_plan(len, bpn, stride, &lp);
-        if (lp.tile_blocks && reinterpret_cast<uintptr_t>(updates) % 16 == 0) {
-#define K3_LOADER_CASE(BPN, T, D, CONS)                                                         \
-    case BPN: {                                                                                 \
-        dim3 grid(lp.tile_blocks + lp.has_remainder), block((1 + CONS) * 64);                   \
-        if (ept == 411)                                                                         \
-            hipLaunchKernelGGL((k3_aggregate_loader<BPN, T, D, CONS, 2>), grid, block, 0, 0,    \
-                               acc, updates, stride, n_updates, len, uint32_t(lp.n_tiles));     \
-        else                                                                                    \
-            hipLaunchKernelGGL((k3_aggregate_loader<BPN, T, D, CONS, 0>), grid, block, 0, 0,    \
-                               acc, updates, stride, n_updates, len, uint32_t(lp.n_tiles));     \
-        return hipGetLastError();                                                               \
-    }
-            switch (bpn) {
-                K3_LOADER_CONFIGS(K3_LOADER_CASE)
-                default:;
-            }
-#undef K3_LOADER_CASE
-        }
-        ept = 0;  // no full tile, no loader kernel or misaligned rows: generic kernel
+        // no full tile, no such kernel for this bpn, or a base or stride that
+        // is not 16-byte aligned: the generic kernel
+        ept = 0;
     }
 #define K3_LAUNCH(BPN, EPT)                                                                     \
     {                                                                                           \
@@ -2135,6 +2030,8 @@ hipError_t xhip_k3_aggregate(uint64_t* acc, const uint8_t* updates, uint64_t str
 // default EPT per BPN chosen so EPT*BPN % 16 == 0 (16B-aligned dwordx4 thread
 // chunks) while keeping register pressure low; ept<=0 picks the default,
 // larger measured-variant values available for sweeps (scripts/k3_sweep.py).
+// Every ept that is not listed for its bpn runs the default too; that includes
+// 201 / 202, the codes of the retired LDS-staged kernel.
 #define K3_CASE(BPN, DEFEPT, ALT1, ALT2)                                                        \
     case BPN:                                                                                   \
         if (ept == ALT1)                                                                        \
@@ -2144,39 +2041,6 @@ hipError_t xhip_k3_aggregate(uint64_t* acc, const uint8_t* updates, uint64_t str
         else                                                                                    \
             K3_LAUNCH(BPN, DEFEPT)                                                              \
         break;
-    // ept=201/202: LDS-staged variant with E=2048/4096-element tiles (16B-
-    // aligned rows required; alignment is guaranteed by the pool allocator)
-    if (ept == 201 || ept == 202) {
-        uintptr_t base = reinterpret_cast<uintptr_t>(updates);
-        if ((base % 16) == 0 && (stride % 16) == 0) {
-#define K3_LDS_CASE(BPN)                                                                        \
-    case BPN: {                                                                                 \
-        if (ept == 201) {                                                                       \
-            uint32_t wgs = ceil_div_u32((len + 2047) / 2048, 1);                                \
-            hipLaunchKernelGGL((k3_aggregate_lds<BPN, 2048>), dim3(wgs), dim3(256), 0, 0, acc,  \
-                               updates, stride, n_updates, len);                                \
-        } else {                                                                                \
-            uint32_t wgs = ceil_div_u32((len + 4095) / 4096, 1);                                \
-            hipLaunchKernelGGL((k3_aggregate_lds<BPN, 4096>), dim3(wgs), dim3(256), 0, 0, acc,  \
-                               updates, stride, n_updates, len);                                \
-        }                                                                                       \
-        return hipGetLastError();                                                               \
-    }
-            switch (bpn) {
-                K3_LDS_CASE(1)
-                K3_LDS_CASE(2)
-                K3_LDS_CASE(3)
-                K3_LDS_CASE(4)
-                K3_LDS_CASE(5)
-                K3_LDS_CASE(6)
-                K3_LDS_CASE(7)
-                K3_LDS_CASE(8)
-                default:;
-            }
-#undef K3_LDS_CASE
-        }
-        ept = 0;  // misaligned: fall through to the generic kernel
-    }
     switch (bpn) {
         K3_CASE(1, 16, 32, 16)
         K3_CASE(2, 8, 16, 8)
