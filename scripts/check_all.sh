@@ -23,6 +23,10 @@ build/model_codec_sanitize
 g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
     -Ixaynet_amd/csrc scripts/model_decode_sanitize.cpp -o build/model_decode_sanitize
 build/model_decode_sanitize
+# and the rational mode's (mc_read_ratio): the gather and both divisions
+g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
+    -Ixaynet_amd/csrc scripts/model_ratio_sanitize.cpp -o build/model_ratio_sanitize
+build/model_ratio_sanitize
 # the exact float unmask's element function (ur_round), float and double, L = 1..5
 g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
     -Ixaynet_amd/csrc scripts/unmask_round_sanitize.cpp -o build/unmask_round_sanitize

@@ -17,7 +17,18 @@ cpu path is measured at 1M only; its 25M figure is 25 times that, marked `~`.
 
 Run: python scripts/model_decode_bench.py [--out FILE] [--small]
 The table replaces the text between the `table:begin` / `table:end` markers
-of FILE (default profiles/r13_model_decode.md)."""
+of FILE (default profiles/r13_model_decode.md).
+
+--rational measures the rational mode instead (default FILE
+profiles/r16_model_decode_rational.md): 1M and 25M f32 weights as d / Q with
+one three-digit Q, 12 words an element, which no default-mode kernel takes.
+  cpu+h2d  the path without the mode: sdk.decode_model and the upload of its
+           result (ParticipantAccel's fallback), measured at 1M; the 25M
+           figure is 25 times that, marked `~`
+  gpu      eng.decode_model(body, 0, rational=True), pinned staging
+in cpu+h2d, gpu, gpu, cpu+h2d order per round, and split into the upload and
+the kernels alone, next to the default kernels on a canonical body of as many
+f32 weights (alternated with the rational ones, call by call)."""
 import argparse
 import os
 import sys
@@ -135,13 +146,106 @@ def run_case(eng, n, name, lines, cpu_1m):
     return t
 
 
+def rational_body(n, seed=16):
+    """head | n elements +-d / Q: Q = 3 * 2^94 + 12345 (three digits), d three
+    random digits below Q, so every weight is in (-1, 1) and none is dyadic."""
+    rng = np.random.default_rng(seed)
+    q = [(3 * 2**94 + 12345) >> (32 * i) & 0xFFFFFFFF for i in range(3)]
+    words = np.empty((n, 12), dtype="<u4")
+    words[:, 0] = 2 * rng.integers(0, 2, n, dtype=np.uint32)
+    words[:, 1:3] = (3, 0)
+    words[:, 3:5] = rng.integers(0, 2**32, (n, 2), dtype=np.uint32)
+    words[:, 5] = rng.integers(1, q[2], n, dtype=np.uint32)  # below Q's top digit
+    words[:, 6:9] = (2, 3, 0)
+    words[:, 9:12] = q
+    return b"\x01" + n.to_bytes(8, "little") + words.tobytes()
+
+
+def run_rational(eng, n, lines, cpu_1m):
+    body = rational_body(n)
+    nbytes = len(body)
+    src = np.frombuffer(body, dtype=np.uint8)
+    canon = sdk.encode_model(weights(n, "float32"))
+    assert eng.decode_model(body, 0) is None  # the mode is what takes it
+    want = sdk.model_codec_decode(body, 0, True) if n <= 1_000_000 else None
+    measure_cpu = n <= 1_000_000
+
+    def cpu():
+        return torch.from_numpy(sdk.decode_model(body, 0)).to("cuda:0")
+
+    t = {"cpu": [], "gpu": []}
+    for rep in range(WARM + REPS):
+        for k in ("cpu", "gpu", "gpu", "cpu"):
+            if k == "cpu" and not measure_cpu:
+                continue
+            ms, got = timed(cpu if k == "cpu" else (lambda: eng.decode_model(body, 0, rational=True)))
+            assert got is not None
+            if k == "gpu" and rep == 0 and want is not None:
+                assert np.array_equal(got.cpu().numpy().view(np.uint32), want.view(np.uint32))
+            if rep >= WARM:
+                t[k].append(ms)
+            del got
+    if not measure_cpu:
+        t["cpu"] = [25 * x for x in cpu_1m]
+
+    # the parts: the rational kernels on this body and the default kernels on
+    # the canonical one, each on buffers of its own, call by call
+    bufs = {}
+    for name, b in (("ratio", body), ("canon", canon)):
+        dev = torch.empty(3 + len(b) + 1, dtype=torch.uint8, device="cuda:0")
+        plan = _hip._model_decode_plan((len(b) - 9) // 4)
+        work = torch.empty(plan["work_bytes"], dtype=torch.uint8, device="cuda:0")
+        eng._upload_body(np.frombuffer(b, dtype=np.uint8), dev, "pinned")
+        bufs[name] = (dev, work, len(b))
+    out = torch.empty(n, dtype=torch.int64, device="cuda:0")
+    p = {"h2d": [], "ratio": [], "canon": []}
+    for rep in range(WARM + 2 * REPS):
+        ms, _ = timed(lambda: eng._upload_body(src, bufs["ratio"][0], "pinned"))
+        p["h2d"].append(ms)
+        for name in ("ratio", "canon", "canon", "ratio"):
+            dev, work, nb = bufs[name]
+            ms, rejected = timed(lambda: _hip._model_decode(
+                dev.data_ptr() + 3, nb, 0, n, work.data_ptr(), out.data_ptr(), 0, name == "ratio"))
+            assert rejected == 0
+            if rep >= WARM:
+                p[name].append(ms)
+    label = f"{n // 1_000_000}M float32"
+    lines.append(f"| {label} | {nbytes / 1e6:.1f} | {fmt(t['cpu'], '' if measure_cpu else '~')} | "
+                 f"{fmt(t['gpu'])} | {stats(t['cpu'])[0] / stats(t['gpu'])[0]:.1f}x | "
+                 f"{fmt(p['h2d'][WARM:])} | {fmt(p['ratio'])} | {len(canon) / 1e6:.1f} | "
+                 f"{fmt(p['canon'])} |")
+    print(lines[-1], flush=True)
+    return t
+
+
+def main_rational(eng, args):
+    lines = ["| weights | body (MB) | cpu decode + upload (ms) | gpu, rational (ms) | cpu / gpu | "
+             "H2D pinned (ms) | rational kernels (ms) | canonical body (MB) | "
+             "default kernels on it (ms) |",
+             "|---|---|---|---|---|---|---|---|---|"]
+    print("\n".join(lines), flush=True)
+    cpu_1m = None
+    for n in (1_000_000, 25_000_000):
+        if args.small and n > 1_000_000:
+            continue
+        t = run_rational(eng, n, lines, cpu_1m)
+        cpu_1m = cpu_1m or t["cpu"]
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r13_model_decode.md"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--small", action="store_true", help="the 1M cases only")
+    ap.add_argument("--rational", action="store_true", help="the rational mode's table")
     args = ap.parse_args()
+    args.out = args.out or os.path.join(
+        ROOT, "profiles", "r16_model_decode_rational.md" if args.rational else "r13_model_decode.md")
     cfg = mk.MaskConfig(1, 0, 0, 3)
     eng = GpuMaskedAggregator(cfg, cfg, 16, device="cuda:0")  # decode_model takes any length
+    if args.rational:
+        write_table(args.out, "\n".join(main_rational(eng, args)))
+        return
     lines = ["| weights | body (MB) | cpu decode (ms) | gpu, pageable (ms) | gpu, pinned (ms) | "
              "gpu, registered (ms) | H2D pageable (ms) | H2D pinned (ms) | H2D registered (ms) | "
              "kernels (ms) | fastest | cpu / fastest gpu |",
@@ -154,13 +258,16 @@ def main():
         t = run_case(eng, n, name, lines, cpu_1m.get(name))
         if n == 1_000_000:
             cpu_1m[name] = t["cpu"]
-    table = "\n".join(lines)
-    text = open(args.out).read() if os.path.exists(args.out) else f"{BEGIN}\n{END}\n"
+    write_table(args.out, "\n".join(lines))
+
+
+def write_table(path, table):
+    text = open(path).read() if os.path.exists(path) else f"{BEGIN}\n{END}\n"
     if BEGIN in text and END in text:
         text = text[: text.index(BEGIN) + len(BEGIN)] + "\n" + table + "\n" + text[text.index(END):]
     else:
         text += f"\n{BEGIN}\n{table}\n{END}\n"
-    with open(args.out, "w") as f:
+    with open(path, "w") as f:
         f.write(text)
 
 

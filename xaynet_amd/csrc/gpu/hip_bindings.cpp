@@ -506,11 +506,12 @@ PYBIND11_MODULE(_hip, m) {
     // "rejected": the body is not head 01, u64 len, len canonical elements of
     // the dtype and nothing after; `out` is then unspecified. `work` holds
     // _model_decode_plan((nbytes - 9) / 4, tile_blocks)["work_bytes"] bytes.
-    // One status word is read back after the last kernel.
+    // One status word is read back after the last kernel. `rational` accepts
+    // any rational element of up to ten digits a side instead (kernels.h).
     m.def(
         "_model_decode",
         [](uintptr_t body, uint64_t nbytes, int dtype, uint64_t len, uintptr_t work,
-           uintptr_t out, uint32_t tile_blocks) -> uint32_t {
+           uintptr_t out, uint32_t tile_blocks, bool rational) -> uint32_t {
             if (dtype < 0 || dtype > 3) throw py::value_error("dtype must be 0..3");
             if (tile_blocks > XHIP_K7D_TILE_BLOCKS)
                 throw py::value_error("tile_blocks is at most " +
@@ -519,12 +520,12 @@ PYBIND11_MODULE(_hip, m) {
             uint32_t rejected = 1;
             check(xhip_k7d_decode(reinterpret_cast<const void*>(body), nbytes, dtype, len,
                                   reinterpret_cast<void*>(work), reinterpret_cast<void*>(out),
-                                  tile_blocks, &rejected),
+                                  tile_blocks, rational, &rejected),
                   "k7d_decode");
             return rejected;
         },
         py::arg("body"), py::arg("nbytes"), py::arg("dtype"), py::arg("len"), py::arg("work"),
-        py::arg("out"), py::arg("tile_blocks") = 0);
+        py::arg("out"), py::arg("tile_blocks") = 0, py::arg("rational") = false);
 
     // private: how _model_decode splits `words` element words (XhipK7dPlan)
     m.def(

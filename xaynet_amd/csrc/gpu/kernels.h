@@ -195,8 +195,13 @@ void xhip_k7d_plan(uint64_t words, uint32_t tile_blocks, XhipK7dPlan* plan);
 // the last kernel (the caller with the bytes on the host checks the head
 // there too). No word at or
 // past body + nbytes is read.
+// `rational` widens "canonical" to any Ratio<BigInt> with a positive
+// denominator and at most ten digits a side (mc_read_ratio, model_codec.h):
+// floats are the exact rational rounded once, integers its quotient truncated
+// toward zero, rejected where the dtype does not hold it. On a canonical body
+// both modes give the same weights.
 hipError_t xhip_k7d_decode(const void* body, uint64_t nbytes, int dtype, uint64_t n, void* work,
-                           void* out, uint32_t tile_blocks, uint32_t* rejected);
+                           void* out, uint32_t tile_blocks, bool rational, uint32_t* rejected);
 
 // ---- every width: u64, u128 and multi-limb orders below 2^320 ----
 //

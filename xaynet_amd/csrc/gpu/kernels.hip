@@ -1598,7 +1598,8 @@ __global__ void __launch_bounds__(K7_BLOCK) k7_model_emit(
 //   k7d_replay      per tile, from its known entry: each block's true entry
 //                   and element base; the last tile checks the count against n
 //   k7d_emit        a block lists its element starts from its entry, then
-//                   thread j decodes element j to out[base + j]
+//                   thread j decodes element j to out[base + j]; in the
+//                   rational mode any rational of up to ten digits a side
 // One tile needs neither k7d_tile_maps nor k7d_walk_tiles. A map entry is one
 // u32: exit offset (6 bits) | valid << 6 | elements << 7. Any defect (a span
 // of 0 on a chain, a chain that does not end exactly on the last word, a wrong
@@ -1746,7 +1747,12 @@ __global__ void __launch_bounds__(K7D_THREADS) k7d_replay(
     if (!valid || (first + nb == blocks && base != n)) *status = 1;
 }
 
-template <typename T>
+// RATIO: the rational mode. The thread's element is any Ratio<BigInt> of up to
+// ten digits a side (mc_read_ratio), its digits gathered from the same LDS
+// words into five-limb registers and divided there: once-rounded floats,
+// truncated integers. A longer element passes where it is canonical
+// (mc_read_rational).
+template <typename T, bool RATIO = false>
 __global__ void __launch_bounds__(K7D_THREADS) k7d_emit(
     const uint32_t* __restrict__ buf, uint64_t W, uint64_t n,
     const uint64_t* __restrict__ blk_base, const uint32_t* __restrict__ blk_entry,
@@ -1774,7 +1780,12 @@ __global__ void __launch_bounds__(K7D_THREADS) k7d_emit(
         const uint32_t p = starts[j];
         T v;
         // base + j < n holds wherever the count check passed
-        if (base + j < n && mc_read<T>(lds_w + p, lds_span[p], &v))
+        bool ok = base + j < n;
+        if constexpr (RATIO)
+            ok = ok && mc_read_rational<T>(lds_w + p, lds_span[p], &v);
+        else
+            ok = ok && mc_read<T>(lds_w + p, lds_span[p], &v);
+        if (ok)
             out[base + j] = v;
         else
             *status = 1;
@@ -2357,7 +2368,7 @@ void xhip_k7d_plan(uint64_t words, uint32_t tile_blocks, XhipK7dPlan* plan) {
 }
 
 hipError_t xhip_k7d_decode(const void* body, uint64_t nbytes, int dtype, uint64_t n, void* work,
-                           void* out, uint32_t tile_blocks, uint32_t* rejected) {
+                           void* out, uint32_t tile_blocks, bool rational, uint32_t* rejected) {
     *rejected = 1;
     if (dtype < 0 || dtype > 3 || tile_blocks > K7D_TILE_MAX) return hipErrorInvalidValue;
     if (nbytes < 9 || (nbytes - 9) % 4 != 0) return hipSuccess;
@@ -2407,8 +2418,12 @@ hipError_t xhip_k7d_decode(const void* body, uint64_t nbytes, int dtype, uint64_
                        blk_base, blk_entry, status);
     e = dispatch_dtype(dtype, [&](auto t) {
         using T = typename decltype(t)::type;
-        hipLaunchKernelGGL(k7d_emit<T>, dim3(blocks), dim3(K7D_THREADS), 0, 0, buf, W, n,
-                           blk_base, blk_entry, static_cast<T*>(out), status);
+        if (rational)
+            hipLaunchKernelGGL((k7d_emit<T, true>), dim3(blocks), dim3(K7D_THREADS), 0, 0, buf, W,
+                               n, blk_base, blk_entry, static_cast<T*>(out), status);
+        else
+            hipLaunchKernelGGL(k7d_emit<T>, dim3(blocks), dim3(K7D_THREADS), 0, 0, buf, W, n,
+                               blk_base, blk_entry, static_cast<T*>(out), status);
         return hipGetLastError();
     });
     if (e != hipSuccess) return e;

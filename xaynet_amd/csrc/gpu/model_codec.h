@@ -21,6 +21,8 @@
 #include <cstdint>
 #include <cstring>
 
+#include "unmask_round.h"  // ur_round, limbs.h
+
 #if defined(__HIPCC__)
 #define MC_FN __host__ __device__ __forceinline__
 #else
@@ -238,4 +240,111 @@ MC_FN bool mc_read(const uint32_t* w, uint32_t len, T* out) {
         e = -int(k);
     }
     return mc_compose(m, e, sign == 0, out);
+}
+
+// ---- the rational mode: any Ratio<BigInt> of up to MC_RATIO_DIGITS digits a side
+
+// five u64 limbs a number, the project's MAX_BYTES_PER_NUMBER
+#define MC_RATIO_DIGITS 10
+#define MC_RATIO_LIMBS 5
+
+// `count` <= MC_RATIO_DIGITS little-endian base 2^32 digits at d as limbs;
+// reads d[0..count) only
+MC_FN limbs<MC_RATIO_LIMBS> mc_gather(const uint32_t* d, uint32_t count) {
+    limbs<MC_RATIO_LIMBS> r;
+#pragma unroll
+    for (int j = 0; j < MC_RATIO_LIMBS; ++j) {
+        const uint64_t lo = uint32_t(2 * j) < count ? d[2 * j] : 0u;
+        const uint64_t hi = uint32_t(2 * j + 1) < count ? d[2 * j + 1] : 0u;
+        r.w[j] = lo | (hi << 32);
+    }
+    return r;
+}
+
+// floor(mag / q), or false where it is 2^64 or more. mag = head * 2^64 + low
+// with head < q, so head is the first remainder and the 64 bits of low are
+// shifted in one restoring step each, on L + 1 limbs like ur_round: every
+// element takes the same 64 steps.
+template <int L>
+MC_FN bool mc_trunc_div(const limbs<L>& mag, const limbs<L>& q, uint64_t* quot) {
+    limbs<L> head = mag;
+    uint64_t low = ml_shr_limb(head);
+    if (ml_geq(head, q)) return false;
+    limbs<L + 1> rem = ml_resize<L + 1>(head);
+    const limbs<L + 1> den = ml_resize<L + 1>(q);
+    uint64_t x = 0;
+#pragma unroll 1
+    for (int k = 0; k < 64; ++k) {
+        ml_shl_bits(rem, 1);  // rem < q < 2^(64L): fits L + 1 limbs
+        rem.w[0] |= low >> 63;
+        low <<= 1;
+        limbs<L + 1> trial = rem;
+        const uint64_t borrow = ml_sub(trial, den);
+        if (!borrow) rem = trial;
+        x = (x << 1) | (borrow ^ 1);
+    }
+    *quot = x;
+    return true;
+}
+
+// +-mag / q as a T: floats rounded once (nearest, ties to even, subnormal
+// grid, saturating), integers truncated toward zero and false outside T
+template <int L>
+MC_FN bool mc_quotient(bool neg, const limbs<L>& mag, const limbs<L>& q, float* out) {
+    *out = ur_round<float, L>(neg, mag, q);
+    return true;
+}
+
+template <int L>
+MC_FN bool mc_quotient(bool neg, const limbs<L>& mag, const limbs<L>& q, double* out) {
+    *out = ur_round<double, L>(neg, mag, q);
+    return true;
+}
+
+template <int L>
+MC_FN bool mc_quotient(bool neg, const limbs<L>& mag, const limbs<L>& q, int64_t* out) {
+    uint64_t x;
+    if (!mc_trunc_div(mag, q, &x)) return false;
+    if (x > (uint64_t(1) << 63) || (!neg && x == (uint64_t(1) << 63))) return false;
+    *out = int64_t(neg ? uint64_t(0) - x : x);
+    return true;
+}
+
+template <int L>
+MC_FN bool mc_quotient(bool neg, const limbs<L>& mag, const limbs<L>& q, int32_t* out) {
+    uint64_t x;
+    if (!mc_trunc_div(mag, q, &x)) return false;
+    if (x > (uint64_t(1) << 31) || (!neg && x == (uint64_t(1) << 31))) return false;
+    *out = int32_t(uint32_t(neg ? uint64_t(0) - x : x));
+    return true;
+}
+
+// True exactly when the len words at w are a Ratio<BigInt> with a Plus
+// denominator, no leading zero digit and at most MC_RATIO_DIGITS digits a
+// side; *out is then its value as a T (mc_quotient), reduced or not, and +0
+// for zero over anything. False also where an integer T does not hold the
+// quotient. Reads w[0..len) only.
+template <typename T>
+MC_FN bool mc_read_ratio(const uint32_t* w, uint32_t len, T* out) {
+    if (len < 7 || len > MC_MAX_WORDS) return false;
+    const uint32_t sign = w[0], nd = w[1];
+    if (w[2] != 0 || nd > MC_RATIO_DIGITS || nd > len - 7) return false;
+    const uint32_t dd = w[4 + nd];
+    if (w[3 + nd] != 2 || w[5 + nd] != 0 || dd > MC_RATIO_DIGITS || dd != len - 6 - nd)
+        return false;
+    const uint32_t* num = w + 3;
+    const uint32_t* den = w + 6 + nd;
+    if (den[dd - 1] == 0) return false;
+    // NoSign is the number without digits; Minus and Plus have a top digit
+    if (sign == 1 ? nd != 0 : (sign > 2 || nd == 0 || num[nd - 1] == 0)) return false;
+    return mc_quotient<MC_RATIO_LIMBS>(sign == 0, mc_gather(num, nd), mc_gather(den, dd), out);
+}
+
+// The element of the rational mode (k7d_emit<T, true>, model_codec_decode):
+// mc_read_ratio, and past its ten digits the canonical elements, which reach
+// 34 (a double below 2^-320), so that a canonical body decodes in either mode.
+// Where both accept they agree: a canonical element is a value of T exactly.
+template <typename T>
+MC_FN bool mc_read_rational(const uint32_t* w, uint32_t len, T* out) {
+    return mc_read_ratio<T>(w, len, out) || mc_read<T>(w, len, out);
 }

@@ -108,8 +108,9 @@ static auto codec_dispatch(const py::array& w, F f) {
 
 // The strict decoder: the sequential walk over mc_span / mc_read that the K7d
 // kernels run in parallel. None unless the body is head 01, u64 n, exactly n
-// canonical elements of T and nothing after.
-template <typename T>
+// canonical elements of T and nothing after. RATIO: the rational mode, the
+// same walk with mc_read_rational.
+template <typename T, bool RATIO>
 static py::object codec_decode(const uint8_t* body, size_t nbytes) {
     if (nbytes < 9 || body[0] != 1 || (nbytes - 9) % 4 != 0) return py::none();
     uint64_t n;
@@ -126,7 +127,10 @@ static py::object codec_decode(const uint8_t* body, size_t nbytes) {
         const uint64_t left = total - at;
         const uint32_t len =
             mc_span(words.data() + at, left > MC_MAX_WORDS ? MC_MAX_WORDS : uint32_t(left));
-        if (len == 0 || !mc_read<T>(words.data() + at, len, dst + i)) return py::none();
+        if (len == 0) return py::none();
+        if (!(RATIO ? mc_read_rational<T>(words.data() + at, len, dst + i)
+                    : mc_read<T>(words.data() + at, len, dst + i)))
+            return py::none();
         at += len;
     }
     if (at != total) return py::none();
@@ -398,20 +402,26 @@ void bind_sdk(py::module_& m) {
     // The GPU's model decoder on the host: the weights of a canonical body
     // (what model_codec_encode writes) as an ndarray of dtype 0..3, None for
     // any other body. message/bincode.cpp's decoder accepts more: any rational.
-    s.def("model_codec_decode", [](py::buffer body, int dtype) -> py::object {
+    // rational=True accepts every rational of up to ten digits a side with a
+    // positive denominator and rounds it once (mc_read_rational).
+    s.def("model_codec_decode", [](py::buffer body, int dtype, bool rational) -> py::object {
         py::buffer_info bi = body.request();
         if (!PyBuffer_IsContiguous(bi.view(), 'C'))
             throw py::value_error("body must be C-contiguous");
         const uint8_t* bp = static_cast<const uint8_t*>(bi.ptr);
         const size_t blen = size_t(bi.size * bi.itemsize);
-        switch (dtype) {
-            case 0: return codec_decode<float>(bp, blen);
-            case 1: return codec_decode<double>(bp, blen);
-            case 2: return codec_decode<int32_t>(bp, blen);
-            case 3: return codec_decode<int64_t>(bp, blen);
+        switch (2 * dtype + int(rational)) {
+            case 0: return codec_decode<float, false>(bp, blen);
+            case 1: return codec_decode<float, true>(bp, blen);
+            case 2: return codec_decode<double, false>(bp, blen);
+            case 3: return codec_decode<double, true>(bp, blen);
+            case 4: return codec_decode<int32_t, false>(bp, blen);
+            case 5: return codec_decode<int32_t, true>(bp, blen);
+            case 6: return codec_decode<int64_t, false>(bp, blen);
+            case 7: return codec_decode<int64_t, true>(bp, blen);
         }
         throw py::value_error("dtype must be 0..3");
-    }, py::arg("body"), py::arg("dtype"));
+    }, py::arg("body"), py::arg("dtype"), py::arg("rational") = false);
     s.def("model_codec_words", [](const py::array& w) -> py::array_t<uint32_t> {
         return codec_dispatch(w, [](const auto* v, size_t n) {
             std::vector<uint32_t> words = codec_counts(v, n);

@@ -119,19 +119,25 @@ class ParticipantAccel:
             self._dec_engine = GpuMaskedAggregator(cfg, cfg, 16, device=self.device)
         return self._dec_engine
 
-    def decode_model(self, body, dtype: int):
+    def decode_model(self, body, dtype: int, rational: bool = False):
         """The global model of an Option<Model> body as a tensor of
         mask::DataType code `dtype` on this accelerator's device: the values
         _core.sdk.decode_model gives, or None where it gives None. A body in
         the coordinator's own (canonical, dyadic) form is decoded by the K7d
         kernels; any other goes through the CPU decoder and is uploaded. The
-        tensor is the caller's own."""
+        tensor is the caller's own.
+
+        rational=True has the kernels decode every rational body of up to ten
+        digits a side as well, each weight rounded once (the engine's
+        decode_model); only what they reject goes through the CPU decoder,
+        whose floats are rounded more than once."""
         from xaynet_amd import _core
 
         with self._mu:
             try:
                 if memoryview(body).nbytes >= self.DECODE_MIN_BYTES:
-                    t = self._decode_engine().decode_model(body, dtype)
+                    kw = {"rational": True} if rational else {}
+                    t = self._decode_engine().decode_model(body, dtype, **kw)
                     if t is not None:
                         return t.clone()  # the engine's buffer is reused by the next call
             except Exception:  # noqa: BLE001 — CPU fallback

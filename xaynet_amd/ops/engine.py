@@ -430,7 +430,7 @@ class GpuMaskedAggregator(MaskedAggregatorBase):
     # copy). scripts/model_decode_bench.py times all three; the fastest stays.
     _DEC_STAGING = "pinned"
 
-    def decode_model(self, body, dtype: int, tile_blocks: int = 0):
+    def decode_model(self, body, dtype: int, tile_blocks: int = 0, rational: bool = False):
         """The weights of an Option<Model> bincode body, decoded on the GPU
         (K7d), as a device tensor of mask::DataType code `dtype` (0=f32 1=f64
         2=i32 3=i64): bit for bit what _core.sdk.decode_model gives for a body
@@ -440,7 +440,18 @@ class GpuMaskedAggregator(MaskedAggregatorBase):
         not the canonical form of a value of the dtype, more than 2^32
         elements, or a body no device buffer takes. The tensor is a view of a
         cached buffer, valid until the next call on this engine. tile_blocks
-        is a test hook (_hip._model_decode_plan)."""
+        is a test hook (_hip._model_decode_plan).
+
+        rational=True takes any rational element instead, reduced or not:
+        floats are numerator / denominator rounded once (nearest, ties to
+        even, subnormal grid, saturating at the largest finite value),
+        integers the quotient truncated toward zero. None then only for a
+        wrong head or count, trailing bytes, an element of more than 42 words
+        or (unless it is canonical) more than 10 digits a side, a leading
+        zero digit, a denominator
+        that is not positive, an integer quotient outside the dtype, or more
+        than 2^32 elements. A canonical body decodes to the same tensor in
+        both modes."""
         if dtype not in (0, 1, 2, 3):
             raise ValueError("dtype must be 0..3")
         try:
@@ -470,7 +481,7 @@ class GpuMaskedAggregator(MaskedAggregatorBase):
                 return None
             self._upload_body(src, dev)
             rejected = _hip._model_decode(dev.data_ptr() + 3, nbytes, dtype, n, work.data_ptr(),
-                                          out.data_ptr(), tile_blocks)
+                                          out.data_ptr(), tile_blocks, bool(rational))
         if rejected:
             return None
         return out[: n * tdt.itemsize].view(tdt)

@@ -213,11 +213,16 @@ class Participant:
             return None
         return arr.tolist()
 
-    def global_model_tensor(self):
+    def global_model_tensor(self, rational: bool = False):
         """The global model as a 1-D torch tensor of the round's data type, or
         None while there is none: the values of global_model() without the
         list. A gpu=True participant gets it on the accelerator's device,
-        decoded there from the fetched body; any other as a CPU tensor."""
+        decoded there from the fetched body; any other as a CPU tensor.
+        rational=True decodes a body of any rationals of up to ten digits a
+        side with each weight rounded once: on the device for a gpu=True
+        participant (ParticipantAccel.decode_model), through the same element
+        function on the host otherwise. A body that mode rejects goes through
+        the CPU decoder as before."""
         import torch
 
         self._check()
@@ -228,8 +233,12 @@ class Participant:
         if dt < 0:
             raise GlobalModelUnavailable("round parameters unknown")
         if self._accel is not None:
-            return self._accel.decode_model(body, dt)
-        arr = _core.sdk.decode_model(body, dt)
+            return self._accel.decode_model(body, dt, rational) if rational \
+                else self._accel.decode_model(body, dt)
+        # without an accelerator the same element function runs on the host
+        arr = _core.sdk.model_codec_decode(body, dt, True) if rational else None
+        if arr is None:
+            arr = _core.sdk.decode_model(body, dt)
         if arr is None:
             return None
         return torch.from_numpy(arr)
