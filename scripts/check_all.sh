@@ -27,6 +27,11 @@ build/model_decode_sanitize
 g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
     -Ixaynet_amd/csrc scripts/model_ratio_sanitize.cpp -o build/model_ratio_sanitize
 build/model_ratio_sanitize
+# the rational encoder's (ml_gcd, exact division, mc_ratio_write), L = 1..5
+g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
+    -Ixaynet_amd/csrc scripts/model_encode_ratio_sanitize.cpp \
+    -o build/model_encode_ratio_sanitize
+build/model_encode_ratio_sanitize
 # the exact float unmask's element function (ur_round), float and double, L = 1..5
 g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
     -Ixaynet_amd/csrc scripts/unmask_round_sanitize.cpp -o build/unmask_round_sanitize

@@ -499,6 +499,66 @@ PYBIND11_MODULE(_hip, m) {
         },
         py::arg("len"));
 
+    // private (ops/engine.py encode_model_rational, tests): K7r, the digit
+    // planes minus the mask as the exact rational Option<Model> body: every
+    // weight the reduced (t - offset) / divisor. planes, mask, order, offset
+    // and divisor as for unmask in exact mode. Returns the body's length and
+    // writes it at out + 3 if out_bytes >= 3 + that length, as _model_encode
+    // does, with the same 8-byte read-back between count and emit. `work`
+    // holds _model_ratio_plan(len, order)["work_bytes"] bytes.
+    m.def(
+        "_model_encode_rational",
+        [](uintptr_t planes, uintptr_t mask_lo, uintptr_t mask_hi, uint64_t len, int n_planes,
+           const std::string& order, int digit_bits, const std::string& offset,
+           const std::string& divisor, uintptr_t work, uintptr_t out,
+           uint64_t out_bytes) -> uint64_t {
+            Limbs o = parse_order(order, mask_hi);
+            Limbs off = parse_limbs(offset), div = parse_limbs(divisor);
+            check_digit_bits(o, digit_bits);
+            if (off.n > o.n) throw py::value_error("the exact offset must be below the order");
+            if (div.is_zero() || div.n > o.n)
+                throw py::value_error("the exact divisor must be positive and fit the order's "
+                                      "limbs");
+            if (len > (uint64_t(1) << 32))
+                throw py::value_error("a model has at most 2^32 weights");
+            if (len == 0) return 9;
+            py::gil_scoped_release release;
+            void* ws = reinterpret_cast<void*>(work);
+            check(xhip_k7r_count(u64p(planes), u64p(mask_lo), u64p(mask_hi), len, n_planes,
+                                 digit_bits, o.v, off.v, div.v, ws),
+                  "k7r_count");
+            uint64_t words = 0;
+            check(hipMemcpy(&words, ws, sizeof words, hipMemcpyDeviceToHost), "k7r total");
+            const uint64_t body = 9 + 4 * words;
+            if (out_bytes >= 3 + body)
+                check(xhip_k7r_emit(u64p(planes), u64p(mask_lo), u64p(mask_hi), len, n_planes,
+                                    digit_bits, o.v, off.v, div.v, ws, u8p(out), out_bytes),
+                      "k7r_emit");
+            return body;
+        },
+        py::arg("planes"), py::arg("mask_lo"), py::arg("mask_hi"), py::arg("len"),
+        py::arg("n_planes"), py::arg("order"), py::arg("digit_bits"), py::arg("offset"),
+        py::arg("divisor"), py::arg("work"), py::arg("out"), py::arg("out_bytes"));
+
+    // private: how _model_encode_rational splits `len` weights (XhipK7rPlan)
+    m.def(
+        "_model_ratio_plan",
+        [](uint64_t len, const std::string& order) {
+            XhipK7rPlan p;
+            xhip_k7r_plan(len, parse_limbs(order).n, &p);
+            py::dict d;
+            d["block_elems"] = p.scan.block_elems;
+            d["blocks"] = p.scan.blocks;
+            d["scan_levels"] = p.scan.scan_levels;
+            d["tile_blocks"] = p.scan.tile_blocks;
+            d["tiles"] = p.scan.tiles;
+            d["max_words"] = p.max_words;
+            d["gcd_rows"] = p.gcd_rows;
+            d["work_bytes"] = p.work_bytes;
+            return d;
+        },
+        py::arg("len"), py::arg("order"));
+
     // private (ops/engine.py decode_model, tests): K7d, the Option<Model>
     // body of `nbytes` bytes at device address `body` (3 bytes past a 4-byte
     // boundary of its buffer, where _model_encode leaves one) into `len`

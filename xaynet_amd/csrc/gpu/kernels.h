@@ -241,6 +241,35 @@ hipError_t xhip_k4_unmask_limbs(const uint64_t* planes, const uint64_t* mask_lo,
                                 int n_planes, int digit_bits, xhip_limbs order,
                                 xhip_limbs exp_shift, double n_add_shift, double scalar_sum,
                                 xhip_limbs offset, xhip_limbs divisor, double scale);
+// ---- K7r: digit planes -> the exact rational Option<Model> body, L = 1..5 ----
+//
+// Every weight as the reduced rational (t - offset) / divisor, the element
+// Aggregation::unmask + encode_option_model give: the body the CPU plane
+// publishes, byte for byte. planes, mask, order, offset and divisor as for
+// the exact mode of xhip_k4_unmask_limbs (32-bit accumulator planes or
+// compact planes; one u64 mask row for L = 1); no data type: no weight is
+// rounded. The plan is K7's split of `len` elements (`scan`), an element's
+// most words (6 + 4L), and the workspace: K7's, then at byte gcd_rows the L
+// limb rows of len u64 where the count pass leaves each element's gcd for the
+// emit pass. All zero for len == 0, len > 2^32 or L outside 1..5.
+struct XhipK7rPlan {
+    XhipK7Plan scan;
+    uint32_t max_words;
+    uint64_t gcd_rows, work_bytes;
+};
+void xhip_k7r_plan(uint64_t len, int n_limbs, XhipK7rPlan* plan);
+// Counts and scans: afterwards the first u64 of `work` (16-byte aligned,
+// work_bytes long) is the number of u32 words of all elements.
+hipError_t xhip_k7r_count(const uint64_t* planes, const uint64_t* mask_lo,
+                          const uint64_t* mask_hi, uint64_t len, int n_planes, int digit_bits,
+                          xhip_limbs order, xhip_limbs offset, xhip_limbs divisor, void* work);
+// Writes the body at out + 3 (out 4-byte aligned) from the workspace
+// xhip_k7r_count left for the same arguments. Nothing is stored at or past
+// out + out_bytes.
+hipError_t xhip_k7r_emit(const uint64_t* planes, const uint64_t* mask_lo, const uint64_t* mask_hi,
+                         uint64_t len, int n_planes, int digit_bits, xhip_limbs order,
+                         xhip_limbs offset, xhip_limbs divisor, const void* work, uint8_t* out,
+                         uint64_t out_bytes);
 hipError_t xhip_k2_canonicalize_limbs(const uint64_t* planes, uint64_t* out_lo,
                                       uint64_t* out_hi, uint64_t len, int n_planes,
                                       int digit_bits, xhip_limbs order);

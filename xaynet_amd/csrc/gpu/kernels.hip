@@ -1578,6 +1578,98 @@ __global__ void __launch_bounds__(K7_BLOCK) k7_model_emit(
     if (i < len && at + nw <= out_words) mc_write(v, out + at);
 }
 
+// ------------------------------------------- K7r: aggregate -> rational body
+//
+// The Option<Model> body the CPU plane publishes, straight from the digit
+// planes: each weight is the exact rational d / Q, d = t - C, reduced, as
+// Aggregation::unmask and encode_option_model give it. No weight tensor is
+// formed; the kernels do not depend on the model's data type.
+//   k7r_words   the front of k4_unmask_exact (|t - C| and its sign), g =
+//               gcd(|d|, Q) by ml_gcd, |d| / g and Q / g by exact division,
+//               and block b's word total; g goes to limb rows of the workspace
+//   scan        K7's (k7_scan_bases, k1_scan_blocks)
+//   k7r_emit    the front again, g from the workspace, the two divisions, and
+//               each element's words at block base + in-block prefix
+// The emit pass reloads g (8L bytes an element) instead of running the gcd
+// again: at 25M elements the two passes take 9.6 ms against 16.3 ms for L = 5
+// and 0.90 against 0.94 ms for L = 1 (profiles/r17_model_encode_rational.md).
+// An element is 7 .. 6 + 4L words. The body sits at byte 3 of the output
+// buffer as K7's does, so every word is an aligned dword store.
+
+// |t - C| and whether t < C, for element i
+template <int L>
+__device__ __forceinline__ limbs<L> k7r_numerator(
+    const uint64_t* __restrict__ planes, const uint64_t* __restrict__ mask, int64_t mstride,
+    uint64_t len, uint64_t i, int n_planes, int digit_bits, const xhip_limbs& order_c,
+    const xhip_limbs& offset_c, bool& neg) {
+    const limbs<L> order = ml_from<L>(order_c);
+    limbs<L + 1> v = ml_from_planes<L + 1>(planes, len, i, n_planes, digit_bits);
+    limbs<L> t = ml_mod_sub<L>(ml_mod<L>(v, order), ml_load<L>(mask, mstride, i), order);
+    limbs<L> mag = ml_from<L>(offset_c);
+    neg = !ml_geq(t, mag);
+    if (neg) {
+        ml_sub(mag, t);
+        return mag;
+    }
+    ml_sub(t, mag);
+    return t;
+}
+
+template <int L>
+__global__ void __launch_bounds__(K7_BLOCK) k7r_words(
+    const uint64_t* __restrict__ planes, const uint64_t* __restrict__ mask, int64_t mstride,
+    uint64_t len, int n_planes, int digit_bits, xhip_limbs order_c, xhip_limbs offset_c,
+    xhip_limbs divisor_c, uint64_t* __restrict__ gcd_rows, uint32_t* __restrict__ blk_tot) {
+    __shared__ uint32_t wave_tot[K7_BLOCK / WAVE];
+    const uint64_t i = uint64_t(blockIdx.x) * K7_BLOCK + threadIdx.x;
+    uint32_t nw = 0;
+    if (i < len) {
+        bool neg;
+        const limbs<L> mag = k7r_numerator<L>(planes, mask, mstride, len, i, n_planes,
+                                              digit_bits, order_c, offset_c, neg);
+        const limbs<L> q = ml_from<L>(divisor_c);
+        const limbs<L> g = ml_gcd(mag, q);
+        ml_store<L>(gcd_rows, int64_t(len), i, g);
+        nw = mc_reduced_words(mc_ratio_reduce_by(mag, q, g));
+    }
+    block_excl_scan<K7_BLOCK / WAVE>(nw, wave_tot);
+    if (threadIdx.x == 0)
+        blk_tot[blockIdx.x] = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
+}
+
+// bases, in_tile, shift and out_words as for k7_model_emit
+template <int L>
+__global__ void __launch_bounds__(K7_BLOCK) k7r_emit(
+    const uint64_t* __restrict__ planes, const uint64_t* __restrict__ mask, int64_t mstride,
+    uint64_t len, int n_planes, int digit_bits, xhip_limbs order_c, xhip_limbs offset_c,
+    xhip_limbs divisor_c, const uint64_t* __restrict__ gcd_rows,
+    const uint64_t* __restrict__ bases, const uint32_t* __restrict__ in_tile, int shift,
+    uint32_t* __restrict__ out, uint64_t out_words) {
+    __shared__ uint32_t wave_tot[K7_BLOCK / WAVE];
+    const uint64_t i = uint64_t(blockIdx.x) * K7_BLOCK + threadIdx.x;
+    mc_ratio<L> r = mc_ratio<L>{ml_zero<L>(), ml_zero<L>()};
+    bool neg = false;
+    uint32_t nw = 0;
+    if (i < len) {
+        const limbs<L> mag = k7r_numerator<L>(planes, mask, mstride, len, i, n_planes,
+                                              digit_bits, order_c, offset_c, neg);
+        const limbs<L> q = ml_from<L>(divisor_c);
+        r = mc_ratio_reduce_by(mag, q, ml_load<L>(gcd_rows, int64_t(len), i));
+        nw = mc_reduced_words(r);
+    }
+    const uint32_t prefix = block_excl_scan<K7_BLOCK / WAVE>(nw, wave_tot);
+    if (i == 0) {
+        // the head, u8 1 | u64 len, in bytes 3..11
+        reinterpret_cast<uint8_t*>(out)[3] = 1;
+        out[1] = uint32_t(len);
+        out[2] = uint32_t(len >> 32);
+    }
+    const uint64_t at = 3 + bases[blockIdx.x >> shift] +
+                        (in_tile ? in_tile[blockIdx.x] : 0u) + prefix;
+    // the launcher sized `out` from the same counts; never write past it
+    if (i < len && at + nw <= out_words) mc_reduced_write(neg, r, out + at);
+}
+
 // ------------------------------------------- K7d: bincode body -> model
 //
 // The inverse of K7: the Option<Model> body back to weights, accepted only
@@ -2285,25 +2377,14 @@ void xhip_k7_plan(uint64_t len, XhipK7Plan* plan) {
     plan->work_bytes = k7_workspace(*plan).end;
 }
 
-hipError_t xhip_k7_model_count(const void* w, int dtype, uint64_t len, void* work) {
-    XhipK7Plan p;
-    xhip_k7_plan(len, &p);
-    if (p.blocks == 0 || !w || !work || reinterpret_cast<uintptr_t>(work) % 16)
-        return hipErrorInvalidValue;
+// the block totals in the workspace at `base` -> bases and the grand total
+static hipError_t k7_scan(const XhipK7Plan& p, uint8_t* base) {
     const K7Workspace ws = k7_workspace(p);
-    uint8_t* base = static_cast<uint8_t*>(work);
     uint64_t* total = reinterpret_cast<uint64_t*>(base);
     uint64_t* bases = total + 1;
     uint32_t* blk_tot = reinterpret_cast<uint32_t*>(base + ws.blk_tot);
     uint32_t* tile_tot = reinterpret_cast<uint32_t*>(base + ws.tile_tot);
     const uint32_t blocks = uint32_t(p.blocks), tiles = uint32_t(p.tiles);
-    hipError_t e = dispatch_dtype(dtype, [&](auto t) {
-        using T = typename decltype(t)::type;
-        hipLaunchKernelGGL(k7_model_words<T>, dim3(blocks), dim3(K7_BLOCK), 0, 0,
-                           static_cast<const T*>(w), len, blk_tot);
-        return hipGetLastError();
-    });
-    if (e != hipSuccess) return e;
     if (p.scan_levels == 1) {
         hipLaunchKernelGGL(k7_scan_bases, dim3(1), dim3(K7_SCAN_THREADS), 0, 0, blk_tot, blocks,
                            bases, total);
@@ -2313,6 +2394,25 @@ hipError_t xhip_k7_model_count(const void* w, int dtype, uint64_t len, void* wor
     hipLaunchKernelGGL(k7_scan_bases, dim3(1), dim3(K7_SCAN_THREADS), 0, 0, tile_tot, tiles,
                        bases, total);
     return hipGetLastError();
+}
+
+hipError_t xhip_k7_model_count(const void* w, int dtype, uint64_t len, void* work) {
+    XhipK7Plan p;
+    xhip_k7_plan(len, &p);
+    if (p.blocks == 0 || !w || !work || reinterpret_cast<uintptr_t>(work) % 16)
+        return hipErrorInvalidValue;
+    const K7Workspace ws = k7_workspace(p);
+    uint8_t* base = static_cast<uint8_t*>(work);
+    uint32_t* blk_tot = reinterpret_cast<uint32_t*>(base + ws.blk_tot);
+    const uint32_t blocks = uint32_t(p.blocks);
+    hipError_t e = dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL(k7_model_words<T>, dim3(blocks), dim3(K7_BLOCK), 0, 0,
+                           static_cast<const T*>(w), len, blk_tot);
+        return hipGetLastError();
+    });
+    if (e != hipSuccess) return e;
+    return k7_scan(p, base);
 }
 
 hipError_t xhip_k7_model_emit(const void* w, int dtype, uint64_t len, const void* work,
@@ -2702,5 +2802,81 @@ hipError_t xhip_k6_pack_limbs(const uint64_t* in_lo, const uint64_t* in_hi, uint
     return dispatch_limbs<3>(n, [&](auto l) {
         return launch_1d(k6_pack_ml<decltype(l)::value>, len, in_lo, row_stride(in_lo, in_hi),
                          out, len, bpn);
+    });
+}
+
+// ---- K7r: count (gcd) -> scan -> emit, L = 1..5 ----
+
+void xhip_k7r_plan(uint64_t len, int n_limbs, XhipK7rPlan* plan) {
+    *plan = XhipK7rPlan{};
+    if (n_limbs < 1 || n_limbs > ML_MAX_LIMBS) return;
+    xhip_k7_plan(len, &plan->scan);
+    if (plan->scan.blocks == 0) return;
+    plan->max_words = 6 + 4 * uint32_t(n_limbs);
+    // K7's workspace, then the gcd's limb rows on a 16-byte boundary
+    plan->gcd_rows = (plan->scan.work_bytes + 15) / 16 * 16;
+    plan->work_bytes = plan->gcd_rows + 8 * uint64_t(n_limbs) * len;
+}
+
+// what both launchers refuse: the plane window of k4_unmask_exact, and an
+// offset or divisor beyond the order's limbs
+static bool bad_k7r(int n, int n_planes, int digit_bits, const xhip_limbs& offset,
+                    const xhip_limbs& divisor) {
+    const bool no_divisor = n_limbs_of(divisor) == 1 && divisor.w[0] == 0;
+    return bad_planes_ml(n, n_planes, digit_bits) || (n == 1 && digit_bits != 32) ||
+           n_limbs_of(offset) > n || n_limbs_of(divisor) > n || no_divisor;
+}
+
+hipError_t xhip_k7r_count(const uint64_t* planes, const uint64_t* mask_lo,
+                          const uint64_t* mask_hi, uint64_t len, int n_planes, int digit_bits,
+                          xhip_limbs order, xhip_limbs offset, xhip_limbs divisor, void* work) {
+    const int n = n_limbs_of(order);
+    XhipK7rPlan p;
+    xhip_k7r_plan(len, n, &p);
+    if (p.scan.blocks == 0 || !planes || !mask_lo || (n > 1 && !mask_hi) || !work ||
+        reinterpret_cast<uintptr_t>(work) % 16 || bad_k7r(n, n_planes, digit_bits, offset, divisor))
+        return hipErrorInvalidValue;
+    uint8_t* base = static_cast<uint8_t*>(work);
+    uint32_t* blk_tot = reinterpret_cast<uint32_t*>(base + k7_workspace(p.scan).blk_tot);
+    uint64_t* gcd_rows = reinterpret_cast<uint64_t*>(base + p.gcd_rows);
+    const int64_t mstride = n == 1 ? 0 : row_stride(mask_lo, mask_hi);
+    hipError_t e = dispatch_limbs<1>(n, [&](auto l) {
+        constexpr int L = decltype(l)::value;
+        hipLaunchKernelGGL(k7r_words<L>,
+                           dim3(uint32_t(p.scan.blocks)), dim3(K7_BLOCK), 0, 0, planes, mask_lo,
+                           mstride, len, n_planes, digit_bits, order, offset, divisor, gcd_rows,
+                           blk_tot);
+        return hipGetLastError();
+    });
+    if (e != hipSuccess) return e;
+    return k7_scan(p.scan, base);
+}
+
+hipError_t xhip_k7r_emit(const uint64_t* planes, const uint64_t* mask_lo, const uint64_t* mask_hi,
+                         uint64_t len, int n_planes, int digit_bits, xhip_limbs order,
+                         xhip_limbs offset, xhip_limbs divisor, const void* work, uint8_t* out,
+                         uint64_t out_bytes) {
+    const int n = n_limbs_of(order);
+    XhipK7rPlan p;
+    xhip_k7r_plan(len, n, &p);
+    if (p.scan.blocks == 0 || !planes || !mask_lo || (n > 1 && !mask_hi) || !work || !out ||
+        reinterpret_cast<uintptr_t>(out) % 4 || out_bytes < 12 ||
+        bad_k7r(n, n_planes, digit_bits, offset, divisor))
+        return hipErrorInvalidValue;
+    const uint8_t* base = static_cast<const uint8_t*>(work);
+    const uint64_t* bases = reinterpret_cast<const uint64_t*>(base) + 1;
+    const uint32_t* blk_tot =
+        reinterpret_cast<const uint32_t*>(base + k7_workspace(p.scan).blk_tot);
+    const uint64_t* gcd_rows = reinterpret_cast<const uint64_t*>(base + p.gcd_rows);
+    const bool tiled = p.scan.scan_levels == 2;
+    const int64_t mstride = n == 1 ? 0 : row_stride(mask_lo, mask_hi);
+    return dispatch_limbs<1>(n, [&](auto l) {
+        constexpr int L = decltype(l)::value;
+        hipLaunchKernelGGL(k7r_emit<L>,
+                           dim3(uint32_t(p.scan.blocks)), dim3(K7_BLOCK), 0, 0, planes, mask_lo,
+                           mstride, len, n_planes, digit_bits, order, offset, divisor, gcd_rows,
+                           bases, tiled ? blk_tot : nullptr, tiled ? K7_TILE_SHIFT : 0,
+                           reinterpret_cast<uint32_t*>(out), out_bytes / 4);
+        return hipGetLastError();
     });
 }

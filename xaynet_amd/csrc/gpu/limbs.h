@@ -264,6 +264,96 @@ ML_FN limbs<N> ml_mul_word(const limbs<N>& a, uint64_t x) {
     return r;
 }
 
+// trailing zero bits of a != 0
+template <int N>
+ML_FN int ml_ctz(const limbs<N>& a) {
+    int tz = 0;
+#pragma unroll
+    for (int j = N - 1; j >= 0; --j)
+        if (a.w[j]) tz = 64 * j + __builtin_ctzll(a.w[j]);
+    return tz;
+}
+
+// a >>= s for any s in 0 .. 64*N-1
+template <int N>
+ML_FN void ml_shr(limbs<N>& a, int s) {
+#pragma unroll
+    for (int k = 0; k < N - 1; ++k) {
+        if (s >= 64) {
+            ml_shr_limb(a);
+            s -= 64;
+        }
+    }
+    if (s) ml_shr_bits(a, s);
+}
+
+// gcd(a, b), gcd(0, b) = b: the binary gcd on odd values. With a and b odd,
+// the larger minus the smaller is even and loses at least one bit when its
+// trailing zeros go, so the two bit lengths together shrink every round and
+// 128*N rounds are the bound; random inputs take about 0.7 rounds a bit. No
+// division, no recursion; a round is one compare, one subtraction, one shift.
+template <int N>
+ML_FN limbs<N> ml_gcd(limbs<N> a, limbs<N> b) {
+    if (ml_is_zero(a)) return b;
+    if (ml_is_zero(b)) return a;
+    const int za = ml_ctz(a), zb = ml_ctz(b);
+    ml_shr(a, za);
+    ml_shr(b, zb);
+#pragma unroll 1
+    for (int k = 0; k < 128 * N; ++k) {
+        // b = min(a, b), a = |a - b|
+        limbs<N> diff = a;
+        if (ml_sub(diff, b)) {  // a < b
+            diff = b;
+            ml_sub(diff, a);
+            b = a;
+        }
+        a = diff;
+        if (ml_is_zero(a)) break;
+        ml_shr(a, ml_ctz(a));
+    }
+    ml_shl(b, za < zb ? za : zb);
+    return b;
+}
+
+// 1 / g mod 2^64 for odd g: g itself is right to 3 bits (g * g = 1 mod 8),
+// and each Newton step doubles them
+ML_FN uint64_t ml_inv_word(uint64_t g) {
+    uint64_t inv = g;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) inv *= 2 - g * inv;
+    return inv;
+}
+
+// a / g where g is odd and divides a, with inv = ml_inv_word(g.w[0]): exact
+// division from the low end (Jebelean): limb j of the quotient is the low
+// limb of what is left times inv, and taking that limb's multiple of g away
+// clears the low limb. N rounds of N multiplications, against the 64*N
+// restoring steps of a division from the top.
+template <int N>
+ML_FN limbs<N> ml_div_exact_odd(limbs<N> a, const limbs<N>& g, uint64_t inv) {
+    limbs<N> quot;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        const uint64_t x = a.w[0] * inv;
+        quot.w[j] = x;
+        // x * g <= what is left of a: the product fits, the difference is
+        // exact and its low limb zero
+        ml_sub(a, ml_mul_word(g, x));
+        ml_shr_limb(a);
+    }
+    return quot;
+}
+
+// a / g for any g != 0 that divides a: the shared trailing zeros leave first
+template <int N>
+ML_FN limbs<N> ml_div_exact(limbs<N> a, limbs<N> g) {
+    const int z = ml_ctz(g);
+    ml_shr(a, z);
+    ml_shr(g, z);
+    return ml_div_exact_odd(a, g, ml_inv_word(g.w[0]));
+}
+
 // Nearest double (ties to even) of a: ONE rounding, whatever the width. The
 // value is normalised so its top limb is non-zero and its top bit set; the 64
 // leading bits with everything below OR-ed into bit 0 (a sticky bit, far

@@ -348,3 +348,82 @@ template <typename T>
 MC_FN bool mc_read_rational(const uint32_t* w, uint32_t len, T* out) {
     return mc_read_ratio<T>(w, len, out) || mc_read<T>(w, len, out);
 }
+
+// ---- the rational encoder: +-mag / q -> its reduced Ratio<BigInt> element
+//
+// What the K7r kernels write (kernels.hip) and model_codec_encode_ratio runs
+// on the host: the element write_bigint / write_biguint of message/bincode.cpp
+// give for Ratio::new(+-mag, q), q > 0. Both sides are divided by their gcd,
+//   sign 0/1/2 | count nd | nd digits of mag / g | 2 | count dd | dd digits of q / g
+// with NoSign (1) and no digits for zero, whose denominator reduces to 1: the
+// 7 words of the zero element above. L limbs a side give at most 6 + 4L words.
+
+// mag / g and q / g, g = gcd(mag, q)
+template <int L>
+struct mc_ratio {
+    limbs<L> num, den;
+};
+
+// g must be gcd(mag, q): the odd part of g is inverted once for both sides
+template <int L>
+MC_FN mc_ratio<L> mc_ratio_reduce_by(limbs<L> mag, limbs<L> q, limbs<L> g) {
+    const int z = ml_ctz(g);
+    ml_shr(mag, z);
+    ml_shr(q, z);
+    ml_shr(g, z);
+    const uint64_t inv = ml_inv_word(g.w[0]);
+    return mc_ratio<L>{ml_div_exact_odd(mag, g, inv), ml_div_exact_odd(q, g, inv)};
+}
+
+template <int L>
+MC_FN mc_ratio<L> mc_ratio_reduce(const limbs<L>& mag, const limbs<L>& q) {
+    return mc_ratio_reduce_by(mag, q, ml_gcd(mag, q));
+}
+
+// base 2^32 digits of a, none for zero
+template <int L>
+MC_FN uint32_t mc_ratio_digits(const limbs<L>& a) {
+    return uint32_t(ml_bits(a) + 31) >> 5;
+}
+
+template <int L>
+MC_FN uint32_t mc_reduced_words(const mc_ratio<L>& r) {
+    return 6 + mc_ratio_digits(r.num) + mc_ratio_digits(r.den);
+}
+
+// sign | u64 count | the count's digits; returns the words written. Every
+// limb index is a constant after unrolling, and a digit is stored as it is
+// split off, so nothing is kept in an array.
+template <int L>
+MC_FN uint32_t mc_ratio_put(uint32_t sign, const limbs<L>& a, uint32_t* out) {
+    const uint32_t nd = mc_ratio_digits(a);
+    out[0] = sign;
+    out[1] = nd;
+    out[2] = 0;
+#pragma unroll
+    for (int j = 0; j < L; ++j) {
+        if (uint32_t(2 * j) < nd) out[3 + 2 * j] = uint32_t(a.w[j]);
+        if (uint32_t(2 * j + 1) < nd) out[4 + 2 * j] = uint32_t(a.w[j] >> 32);
+    }
+    return 3 + nd;
+}
+
+// writes the mc_reduced_words(r) words of +-r.num / r.den at out
+template <int L>
+MC_FN void mc_reduced_write(bool neg, const mc_ratio<L>& r, uint32_t* out) {
+    const uint32_t sign = ml_is_zero(r.num) ? 1u : (neg ? 0u : 2u);
+    out += mc_ratio_put(sign, r.num, out);
+    mc_ratio_put(2u, r.den, out);
+}
+
+// the number of u32 words of the element of +-mag / q (q != 0)
+template <int L>
+MC_FN uint32_t mc_ratio_words(const limbs<L>& mag, const limbs<L>& q) {
+    return mc_reduced_words(mc_ratio_reduce(mag, q));
+}
+
+// writes the mc_ratio_words(mag, q) words of the element of +-mag / q at out
+template <int L>
+MC_FN void mc_ratio_write(bool neg, const limbs<L>& mag, const limbs<L>& q, uint32_t* out) {
+    mc_reduced_write(neg, mc_ratio_reduce(mag, q), out);
+}

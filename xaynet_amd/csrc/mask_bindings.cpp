@@ -7,6 +7,7 @@
 #include "gpu/u192.h"
 #include "gpu/unmask_round.h"
 #include "mask/masking.h"
+#include "message/bincode.h"
 
 namespace py = pybind11;
 using namespace xaynet;
@@ -397,6 +398,13 @@ void bind_mask(py::module_& m) {
             for (const Rational& r : a.unmask(mask_obj))
                 out.append(py::make_tuple(r.numer.to_dec(), r.denom.to_dec()));
             return out;
+        })
+        // the Option<Model> bincode body of those rationals: what the CPU
+        // coordinator publishes (coordinator.cpp, Unmask phase)
+        .def("unmask_body", [](const Aggregation& a, const MaskObject& mask_obj) {
+            const RationalModel rm = a.unmask(mask_obj);
+            const Bytes body = bincode::encode_option_model(&rm);
+            return py::bytes(reinterpret_cast<const char*>(body.data()), body.size());
         })
         .def("unmask", [](const Aggregation& a, const MaskObject& mask_obj) -> py::object {
             RationalModel rm = a.unmask(mask_obj);

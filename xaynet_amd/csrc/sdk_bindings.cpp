@@ -137,6 +137,39 @@ static py::object codec_decode(const uint8_t* body, size_t nbytes) {
     return std::move(out);
 }
 
+// The rational encoder at L limbs: the body of the elements +-mags[i] / q,
+// reduced, by the functions the K7r kernels compile.
+template <int L>
+static py::bytes codec_encode_ratio(const std::vector<bool>& negs,
+                                    const std::vector<xhip_limbs>& mags, const xhip_limbs& qv) {
+    const limbs<L> q = ml_from<L>(qv);
+    const size_t n = mags.size();
+    size_t total = 0;
+    for (size_t i = 0; i < n; ++i) total += mc_ratio_words<L>(ml_from<L>(mags[i]), q);
+    std::string body(9 + 4 * total, '\0');
+    body[0] = 1;
+    const uint64_t n64 = n;
+    std::memcpy(&body[1], &n64, 8);
+    // elements start 1 mod 4 in the body: encode into aligned words
+    std::vector<uint32_t> buf(total);
+    size_t at = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const limbs<L> mag = ml_from<L>(mags[i]);
+        mc_ratio_write<L>(negs[i], mag, q, buf.data() + at);
+        at += mc_ratio_words<L>(mag, q);
+    }
+    if (total) std::memcpy(&body[9], buf.data(), 4 * total);
+    return py::bytes(body);
+}
+
+// a Python int in [0, 2^320) as limbs
+static bool codec_limbs(const py::int_& v, xhip_limbs& out) {
+    if (v < py::int_(0) || v.attr("bit_length")().cast<int>() > 64 * ML_MAX_LIMBS) return false;
+    const std::string raw = v.attr("to_bytes")(8 * ML_MAX_LIMBS, "little").cast<std::string>();
+    std::memcpy(out.w, raw.data(), sizeof out.w);  // little-endian hosts only
+    return true;
+}
+
 void bind_sdk(py::module_& m) {
     auto s = m.def_submodule("sdk");
 
@@ -422,6 +455,42 @@ void bind_sdk(py::module_& m) {
         }
         throw py::value_error("dtype must be 0..3");
     }, py::arg("body"), py::arg("dtype"), py::arg("rational") = false);
+    // The GPU's rational encoder (mc_ratio_write, what the K7r kernels
+    // compile) on the host: the Option<Model> body whose element i is the
+    // reduced rational +-mags[i] / q, negative where signs[i]. q is positive
+    // and everything is below 2^320; `limbs` is the instantiation, by default
+    // the fewest limbs that hold q and every magnitude.
+    s.def("model_codec_encode_ratio", [](const py::sequence& signs, const py::sequence& mags,
+                                         const py::int_& q, int n_limbs) -> py::bytes {
+        if (py::len(signs) != py::len(mags))
+            throw py::value_error("model_codec_encode_ratio: one sign per magnitude");
+        xhip_limbs qv;
+        if (q <= py::int_(0) || !codec_limbs(q, qv))
+            throw py::value_error("model_codec_encode_ratio: q in [1, 2^320)");
+        std::vector<xhip_limbs> mv(py::len(mags));
+        std::vector<bool> nv(mv.size());
+        int need = 1;
+        for (int j = 1; j < ML_MAX_LIMBS; ++j)
+            if (qv.w[j]) need = j + 1;
+        for (size_t i = 0; i < mv.size(); ++i) {
+            if (!codec_limbs(py::int_(mags[i]), mv[i]))
+                throw py::value_error("model_codec_encode_ratio: magnitudes in [0, 2^320)");
+            for (int j = need; j < ML_MAX_LIMBS; ++j)
+                if (mv[i].w[j]) need = j + 1;
+            nv[i] = py::cast<bool>(signs[i]);
+        }
+        if (n_limbs == 0) n_limbs = need;
+        if (n_limbs < need || n_limbs > ML_MAX_LIMBS)
+            throw py::value_error("model_codec_encode_ratio: limbs must hold q and every "
+                                  "magnitude (at most 5)");
+        switch (n_limbs) {
+            case 1: return codec_encode_ratio<1>(nv, mv, qv);
+            case 2: return codec_encode_ratio<2>(nv, mv, qv);
+            case 3: return codec_encode_ratio<3>(nv, mv, qv);
+            case 4: return codec_encode_ratio<4>(nv, mv, qv);
+            default: return codec_encode_ratio<5>(nv, mv, qv);
+        }
+    }, py::arg("signs"), py::arg("mags"), py::arg("q"), py::arg("limbs") = 0);
     s.def("model_codec_words", [](const py::array& w) -> py::array_t<uint32_t> {
         return codec_dispatch(w, [](const auto* v, size_t n) {
             std::vector<uint32_t> words = codec_counts(v, n);

@@ -309,6 +309,25 @@ class CpuPlaneAggregator(MaskedAggregatorBase):
             raise ValueError("encode_model takes a contiguous 1-D f32/f64/i32/i64 CPU tensor")
         return np.frombuffer(_core.sdk.encode_model(weights.numpy()), dtype=np.uint8)
 
+    def encode_model_rational(self, mask_values: torch.Tensor, mask_unit: int,
+                              nb_models: int | None = None) -> np.ndarray:
+        """The GPU engine's encode_model_rational: the body whose weights are
+        the exact reduced rationals d / Q, through the host instantiation of
+        the element functions the K7r kernels compile."""
+        nb = self.nb_models if nb_models is None else nb_models
+        return self.encode_model_rational_planes(self.acc, mask_values, mask_unit, nb)
+
+    def encode_model_rational_planes(self, planes: torch.Tensor, mask_values: torch.Tensor,
+                                     mask_unit: int, nb_models: int,
+                                     digit_bits: int = 32) -> np.ndarray:
+        _, vinfo, _ = self._unmask_scalars(mask_unit, nb_models)
+        q = self.exact_divisor(vinfo, 0)
+        order = self.order_int
+        t = (self._planes_to_ints(planes, digit_bits) + order - self._ints(mask_values)) % order
+        d = [int(v) - vinfo["offset"] for v in t]
+        return np.frombuffer(_core.sdk.model_codec_encode_ratio(
+            [v < 0 for v in d], [abs(v) for v in d], q, limbs=self.n_limbs), dtype=np.uint8)
+
     def decode_model(self, body, dtype: int, tile_blocks: int = 0, rational: bool = False):
         """The weights of an Option<Model> bincode body as a CPU tensor of
         mask::DataType code `dtype`, or None unless the body is exactly what

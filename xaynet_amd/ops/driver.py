@@ -32,9 +32,12 @@ LOG = logging.getLogger("xaynet.gpu_driver")
 class GpuCoordinatorDriver(threading.Thread):
     def __init__(self, coordinator, vect_cfg, unit_cfg, length: int,
                  device: str = "cuda:0", pool_size: int = 512, poll_s: float = 0.002,
-                 exact_unmask: bool = False):
+                 exact_unmask: bool = False, rational_model: bool = False):
         super().__init__(daemon=True)
         self.coordinator = coordinator
+        # publish the exact reduced rationals themselves, the CPU plane's body
+        # (engine encode_model_rational, K7r); takes precedence over exact_unmask
+        self.rational_model = bool(rational_model)
         # publish the exact rational weights rounded once (engine exact mode)
         self.exact_unmask = bool(exact_unmask)
         self.eng = GpuMaskedAggregator(vect_cfg, unit_cfg, length, device=device)
@@ -95,12 +98,19 @@ class GpuCoordinatorDriver(threading.Thread):
         mask_vect, mask_unit = self._split_mask_object(mask_bytes)
         t = torch.frombuffer(bytearray(mask_vect), dtype=torch.uint8).to(self.eng.device)
         mask_vals = self.eng.unpack_wire(t)
-        out = self._unmask(mask_vals, mask_unit, nb_models)
-        # K7: the body is encoded on the GPU and lands in pinned host memory;
-        # the coordinator copies that view once, into its own storage
-        self.coordinator.supply_unmasked_model(self.eng.encode_model(out))
+        # K7 / K7r: the body is encoded on the GPU and lands in pinned host
+        # memory; the coordinator copies that view once, into its own storage
+        self.coordinator.supply_unmasked_model(self._body(mask_vals, mask_unit, nb_models))
         self.eng.reset()
         self.rounds_unmasked += 1
+
+    def _body(self, mask_vals, mask_unit: int, nb_models: int):
+        if self.rational_model:
+            try:
+                return self.eng.encode_model_rational(mask_vals, mask_unit, nb_models=nb_models)
+            except ValueError as e:
+                LOG.warning("rational model body refused (%s); rounded weights this round", e)
+        return self.eng.encode_model(self._unmask(mask_vals, mask_unit, nb_models))
 
     def _unmask(self, mask_vals, mask_unit: int, nb_models: int):
         if self.exact_unmask:

@@ -421,6 +421,53 @@ class GpuMaskedAggregator(MaskedAggregatorBase):
             pin.copy_(out[: 3 + body])  # device to pinned host: synchronous
         return pin.numpy()[3:]
 
+    # ---------------- rational model body (K7r) ----------------
+
+    def encode_model_rational(self, mask_values: torch.Tensor, mask_unit: int,
+                              nb_models: int | None = None) -> np.ndarray:
+        """The Option<Model> bincode body of the unmasked aggregate with every
+        weight the exact reduced rational d / Q (K7r): byte for byte what the
+        CPU plane publishes (Aggregation.unmask + encode_option_model), for any
+        data type - no weight is rounded or truncated. Q is exact mode's
+        divisor: ValueError, before any launch, where exp_shift * scalar_sum is
+        no positive integer that fits the order's limbs. Returns a uint8 numpy
+        view of the cached pinned staging buffer encode_model uses, valid
+        until the next call of either on this engine."""
+        nb = self.nb_models if nb_models is None else nb_models
+        return self.encode_model_rational_planes(self.acc, mask_values, mask_unit, nb)
+
+    def encode_model_rational_planes(self, planes: torch.Tensor, mask_values: torch.Tensor,
+                                     mask_unit: int, nb_models: int,
+                                     digit_bits: int = 32) -> np.ndarray:
+        """encode_model_rational of a contiguous [k, n] digit-plane tensor
+        (e.g. a reduce-scattered shard) against matching mask values, as
+        unmask_planes takes them: a whole body of n elements."""
+        lo, hi, n = self._vals(mask_values)
+        ptr, k = self._planes(planes, n, read_bits=digit_bits)
+        # the float rule of exact_divisor, whatever the data type: Q as limbs
+        _, vinfo, _ = self._unmask_scalars(mask_unit, nb_models)
+        q = self.exact_divisor(vinfo, 0)
+        if n == 0:
+            return np.frombuffer(b"\x01" + bytes(8), dtype=np.uint8)
+        args = (ptr, lo, hi, n, k, self.order, digit_bits, str(vinfo["offset"]), str(q))
+        with torch.cuda.device(planes.device):
+            work = self._enc_buffer(
+                "_enc_work", _hip._model_ratio_plan(n, self.order)["work_bytes"])
+            # a first guess: numerator and denominator at half their width
+            out = self._enc_buffer("_enc_dev", 3 + 9 + n * 4 * (6 + 2 * self.n_limbs))
+            body = _hip._model_encode_rational(*args, work.data_ptr(), out.data_ptr(),
+                                               out.numel())
+            if 3 + body > out.numel():  # nothing was written: grow, run again
+                out = self._enc_buffer("_enc_dev", 3 + body)
+                body = _hip._model_encode_rational(*args, work.data_ptr(), out.data_ptr(),
+                                                   out.numel())
+            if self._enc_pin is None or self._enc_pin.numel() < 3 + body:
+                self._enc_pin = torch.empty(3 + body + (3 + body) // 8, dtype=torch.uint8,
+                                            pin_memory=True)
+            pin = self._enc_pin[: 3 + body]
+            pin.copy_(out[: 3 + body])  # device to pinned host: synchronous
+        return pin.numpy()[3:]
+
     # ---------------- model body -> weights (K7d) ----------------
 
     _MODEL_DTYPES = (torch.float32, torch.float64, torch.int32, torch.int64)

@@ -108,11 +108,15 @@ def serve(settings: Settings, ready_event: threading.Event | None = None,
                                          n_workers=n, device_kind="cuda",
                                          exact_unmask=settings.gpu_exact_unmask)
             LOG.info("multi-GPU serve plane: %d devices", n)
+            if settings.gpu_rational_model:
+                LOG.warning("[gpu] rational_model covers the single-GPU plane; the serve plane "
+                            "encodes on the CPU and publishes as before")
         else:
             from xaynet_amd.ops import make_coordinator_driver
 
             driver = make_coordinator_driver(coordinator, c, c, settings.model_length,
-                                             exact_unmask=settings.gpu_exact_unmask)
+                                             exact_unmask=settings.gpu_exact_unmask,
+                                             rational_model=settings.gpu_rational_model)
         driver.start()
     host, port = settings.bind_host_port()
     if settings.api.tls_certificate:

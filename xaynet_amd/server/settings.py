@@ -96,6 +96,7 @@ class Settings:
     gpu: bool = False                   # aggregate on the MI355X data plane
     gpu_devices: int = 0                # 0 = all visible GPUs; N = use N devices
     gpu_exact_unmask: bool = False      # float weights: the exact rational, rounded once
+    gpu_rational_model: bool = False    # the exact reduced rationals themselves (one GPU)
 
     # ------------------------------------------------------------ loading
 
@@ -156,6 +157,7 @@ class Settings:
         s.gpu = bool(gpu.get("enable", False))
         s.gpu_devices = int(gpu.get("devices", 0))
         s.gpu_exact_unmask = bool(gpu.get("exact_unmask", False))
+        s.gpu_rational_model = bool(gpu.get("rational_model", False))
         return s
 
     # ---------------------------------------------------------- validation
