@@ -13,15 +13,17 @@ multi-process serve plane, then times:
 Usage (GPU box):
   python scripts/ingest_bench.py --length 1000000 --clients 512 --workers 1
   python scripts/ingest_bench.py --length 25000000 --clients 64 --plain
+  python scripts/ingest_bench.py --length 25000000 --clients 48 --gpu-open
 """
 import argparse
 import faulthandler
 import json
 import os
+import queue
 import sys
 import threading
 import time
-from concurrent.futures import ThreadPoolExecutor
+from concurrent.futures import Future, ThreadPoolExecutor
 from pathlib import Path
 
 import numpy as np
@@ -59,6 +61,57 @@ def pack_values(vals: np.ndarray, bpn: int) -> bytes:
     return out.tobytes()
 
 
+class GpuOpener:
+    """--gpu-open: the injector threads' sealed messages, opened by one GpuBox
+    (K8) in batches of whatever is waiting, up to `max_batch`. open() blocks
+    its injector thread until the batch is back and returns the plaintext as
+    a host array, or None where the box does not open."""
+
+    def __init__(self, pk, sk, max_batch):
+        from xaynet_amd.ops import GpuBox
+
+        self.box = GpuBox("cuda:0")
+        self.pk, self.sk, self.max_batch = pk, sk, max_batch
+        self.batches = 0
+        self.q = queue.Queue()
+        self.thread = threading.Thread(target=self._loop, daemon=True)
+        self.thread.start()
+
+    def open(self, sealed):
+        fut = Future()
+        self.q.put((sealed, fut))
+        return fut.result()
+
+    def close(self):
+        self.q.put(None)
+        self.thread.join(60)
+
+    def _loop(self):
+        while True:
+            item = self.q.get()
+            if item is None:
+                return
+            batch = [item]
+            while len(batch) < self.max_batch:
+                try:
+                    nxt = self.q.get_nowait()
+                except queue.Empty:
+                    break
+                if nxt is None:
+                    self.q.put(None)
+                    break
+                batch.append(nxt)
+            try:
+                opened, _ = self.box.sealbox_open_batch([b[0] for b in batch], self.pk, self.sk)
+                self.batches += 1
+                for (_, fut), t in zip(batch, opened):
+                    fut.set_result(None if t is None else t.cpu().numpy())
+            except BaseException as e:  # the injector threads must not hang
+                for _, fut in batch:
+                    if not fut.done():
+                        fut.set_exception(e)
+
+
 def main():
     if os.environ.get("INGEST_DEBUG"):
         faulthandler.dump_traceback_later(60, exit=True)
@@ -71,6 +124,10 @@ def main():
     ap.add_argument("--plain", action="store_true",
                     help="skip sealbox (measures post-decrypt pipeline only)")
     ap.add_argument("--slots", type=int, default=32)
+    ap.add_argument("--gpu-open", action="store_true",
+                    help="open the sealed boxes on the GPU (K8, ops.GpuBox) in batches and "
+                         "inject the plaintext with handle_message_bytes")
+    ap.add_argument("--gpu-batch", type=int, default=8, help="most boxes a GPU open batch")
     args = ap.parse_args()
 
     sum_prob, update_prob = 0.5, 0.999
@@ -163,6 +220,21 @@ def main():
     print("injecting...", file=sys.stderr, flush=True)
     # --- timed injection ---
     inject = (coord.handle_message_bytes if args.plain else coord.handle_encrypted_message)
+    opener = None
+    if args.gpu_open and not args.plain:
+        # the round's box key pair leads the coordinator's checkpoint state
+        state = bytes(coord.checkpoint_state())
+        assert state[:32] == cpk
+        opener = GpuOpener(cpk, state[32:64], args.gpu_batch)
+        # load the kernels before the timed window
+        assert opener.open(cr.sealbox_seal(b"warm-up", cpk)).tobytes() == b"warm-up"
+        opener.batches = 0
+
+        def inject(sealed):
+            plain = opener.open(sealed)
+            if plain is None:
+                return int(E.Decrypt)
+            return coord.handle_message_bytes(plain)
     results = []
     t_upd = threading.Thread(target=coord.run_one_phase, daemon=True)
     t_upd.start()
@@ -194,6 +266,8 @@ def main():
 
     driver.stop()
     coord.stop()
+    if opener:
+        opener.close()
 
     inj = t1 - t0
     res = {
@@ -204,6 +278,8 @@ def main():
         "workers": args.workers,
         "device": args.device,
         "sealed": not args.plain,
+        "gpu_open": opener is not None,
+        "gpu_open_batches": opener.batches if opener else 0,
         "inject_threads": args.threads,
         "inject_window_s": round(inj, 3),
         "inject_updates_per_s": round(accepted / inj, 1),

@@ -16,6 +16,7 @@
 #include "crypto/salsa.h"
 #include "crypto/poly1305.h"
 #include "crypto/sha2.h"
+#include "gpu/box_stream.h"
 
 namespace py = pybind11;
 using namespace xaynet;
@@ -152,6 +153,68 @@ PYBIND11_MODULE(_core, m) {
         if (!ok) return py::none();
         return holder;
     });
+    c.def("box_beforenm", [](py::bytes pk, py::bytes sk) {
+        Bytes p = from_pybytes(pk), s = from_pybytes(sk);
+        if (p.size() != 32 || s.size() != 32) throw py::value_error("keys are 32 bytes");
+        uint8_t k[32];
+        box_beforenm(k, p.data(), s.data());
+        return to_pybytes(k, 32);
+    });
+    // tag(16) || cipher
+    c.def("secretbox_seal", [](py::buffer msg, py::bytes nonce, py::bytes key) {
+        py::buffer_info mi = msg.request();
+        Bytes n = from_pybytes(nonce), k = from_pybytes(key);
+        if (n.size() != BOX_NONCE_BYTES || k.size() != 32)
+            throw py::value_error("nonce is 24 bytes, key 32");
+        Bytes out(size_t(mi.size) + BOX_MAC_BYTES);
+        secretbox_seal(out.data(), static_cast<const uint8_t*>(mi.ptr), size_t(mi.size), n.data(),
+                       k.data());
+        return to_pybytes(out.data(), out.size());
+    });
+    c.def("secretbox_open", [](py::buffer cipher, py::bytes nonce, py::bytes key) -> py::object {
+        py::buffer_info ci = cipher.request();
+        Bytes n = from_pybytes(nonce), k = from_pybytes(key);
+        if (n.size() != BOX_NONCE_BYTES || k.size() != 32)
+            throw py::value_error("nonce is 24 bytes, key 32");
+        if (size_t(ci.size) < BOX_MAC_BYTES) return py::none();
+        Bytes out(size_t(ci.size) - BOX_MAC_BYTES);
+        if (!secretbox_open(out.data(), static_cast<const uint8_t*>(ci.ptr), size_t(ci.size),
+                            n.data(), k.data()))
+            return py::none();
+        return to_pybytes(out.data(), out.size());
+    });
+    // The GPU box arithmetic (gpu/box_stream.h) on the host, with tiles of
+    // tile_blocks Salsa blocks (a power of two up to 256; the GPU's is 256).
+    // mode 0 opens tag || cipher (None if the tag fails), 1 seals to
+    // tag || cipher, 2 is Poly1305 alone under the one-time key `key`.
+    c.def(
+        "box_stream_host",
+        [](int mode, py::bytes data, py::bytes nonce, py::bytes key,
+           uint32_t tile_blocks) -> py::object {
+            Bytes d = from_pybytes(data), n = from_pybytes(nonce), k = from_pybytes(key);
+            if (mode < BS_OPEN || mode > BS_MAC) throw py::value_error("mode is 0, 1 or 2");
+            if (k.size() != 32 || (mode != BS_MAC && n.size() != BOX_NONCE_BYTES))
+                throw py::value_error("nonce is 24 bytes, key 32");
+            if (tile_blocks == 0 || tile_blocks > 256 || (tile_blocks & (tile_blocks - 1)))
+                throw py::value_error("tile_blocks is a power of two up to 256");
+            uint8_t tag[16];
+            if (mode == BS_OPEN) {
+                if (d.size() < BOX_MAC_BYTES) return py::none();
+                std::memcpy(tag, d.data(), 16);
+                Bytes out(d.size() - 16);
+                if (!bs_host_box(mode, tile_blocks, k.data(), n.data(), d.data() + 16, out.data(),
+                                 out.size(), tag))
+                    return py::none();
+                return to_pybytes(out.data(), out.size());
+            }
+            Bytes out(16 + (mode == BS_SEAL ? d.size() : 0));
+            bs_host_box(mode, tile_blocks, k.data(), n.data(), d.data(), out.data() + 16, d.size(),
+                        tag);
+            std::memcpy(out.data(), tag, 16);
+            return to_pybytes(out.data(), out.size());
+        },
+        py::arg("mode"), py::arg("data"), py::arg("nonce"), py::arg("key"),
+        py::arg("tile_blocks"));
     c.def("randombytes", [](size_t n) {
         Bytes out(n);
         randombytes(out.data(), n);

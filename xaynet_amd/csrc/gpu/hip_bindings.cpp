@@ -604,6 +604,75 @@ PYBIND11_MODULE(_hip, m) {
         },
         py::arg("words"), py::arg("tile_blocks") = 0);
 
+    // private (ops/box.py): how a batch of boxes of `lens` message bytes is
+    // cut into 16 KiB tiles. Returns (first_tile, work_bytes): each box's
+    // first tile and, last, the tile total; and the workspace _box_run takes.
+    m.def(
+        "_box_plan",
+        [](const std::vector<uint64_t>& lens) {
+            std::vector<uint32_t> first(lens.size() + 1);
+            XhipK8Plan plan;
+            if (xhip_k8_plan(lens.data(), uint32_t(lens.size()), first.data(), &plan) !=
+                hipSuccess)
+                throw py::value_error("a box is at most 2^40 bytes, a batch 2^31 - 1 tiles");
+            return py::make_tuple(first, plan.work_bytes);
+        },
+        py::arg("lens"));
+
+    // private (ops/box.py): K8 over one batch. mode 0 opens, 1 seals, 2 is
+    // Poly1305 alone (kernels.h). keys: 32 bytes a box, nonces: 24 a box
+    // (ignored by mode 2); src_offs / dst_offs: where each box's message
+    // starts in the packed device buffers `src` / `dst` (multiples of 16, the
+    // tag 16 bytes in front of the ciphertext; mode 2 writes its tag at
+    // dst_off). ok: one device u32 a box. Offsets are checked against
+    // src_bytes / dst_bytes before any launch.
+    m.def(
+        "_box_run",
+        [](int mode, const std::string& keys, const std::string& nonces,
+           const std::vector<uint64_t>& lens, const std::vector<uint64_t>& src_offs,
+           const std::vector<uint64_t>& dst_offs, uintptr_t src, uint64_t src_bytes,
+           uintptr_t dst, uint64_t dst_bytes, uintptr_t work, uint64_t work_bytes,
+           uintptr_t ok) {
+            const size_t n = lens.size();
+            if (keys.size() != 32 * n || (mode != 2 && nonces.size() != 24 * n) ||
+                src_offs.size() != n || dst_offs.size() != n)
+                throw py::value_error("_box_run: 32 key bytes, 24 nonce bytes and one offset "
+                                      "pair a box");
+            std::vector<XhipBox> boxes(n);
+            for (size_t i = 0; i < n; ++i) {
+                XhipBox& b = boxes[i];
+                std::memcpy(b.key, keys.data() + 32 * i, 32);
+                std::memset(b.nonce, 0, 24);
+                if (mode != 2) std::memcpy(b.nonce, nonces.data() + 24 * i, 24);
+                b.first_tile = 0;  // the launcher plans the tiles
+                b.reserved = 0;
+                b.src_off = src_offs[i];
+                b.dst_off = dst_offs[i];
+                b.len = lens[i];
+                b.reserved2 = 0;
+            }
+            hipError_t e;
+            {
+                py::gil_scoped_release release;
+                e = xhip_k8_box_run(mode, boxes.data(), uint32_t(n),
+                                    reinterpret_cast<void*>(work), work_bytes, u8p(src),
+                                    src_bytes, u8p(dst), dst_bytes,
+                                    reinterpret_cast<uint32_t*>(ok));
+                // this copy of the keys goes as the device copy does; the
+                // caller's bytes objects are the caller's to forget
+                volatile uint32_t* w = reinterpret_cast<volatile uint32_t*>(boxes.data());
+                for (size_t i = 0; i < n * sizeof(XhipBox) / 4; ++i) w[i] = 0;
+            }
+            if (e == hipErrorInvalidValue)
+                throw py::value_error("_box_run: an offset, a length, the batch or the workspace "
+                                      "does not fit");
+            check(e, "k8_box_run");
+        },
+        py::arg("mode"), py::arg("keys"), py::arg("nonces"), py::arg("lens"),
+        py::arg("src_offs"), py::arg("dst_offs"), py::arg("src"), py::arg("src_bytes"),
+        py::arg("dst"), py::arg("dst_bytes"), py::arg("work"), py::arg("work_bytes"),
+        py::arg("ok"));
+
     // [n_planes][len] digit planes minus the mask -> model weights.
     // dtype follows mask::DataType: 0=F32 1=F64 2=I32 3=I64
     // Bmax configs, and integer outputs of the other bounds, pass `offset` =

@@ -303,4 +303,42 @@ hipError_t xhip_k6_unpack_limbs(const uint8_t* in, uint64_t* out_lo, uint64_t* o
 hipError_t xhip_k6_pack_limbs(const uint64_t* in_lo, const uint64_t* in_hi, uint8_t* out,
                               uint64_t len, int bpn, xhip_limbs order);
 
+// ---- K8: batched XSalsa20-Poly1305 (NaCl secretbox) ----
+//
+// One box of a batch, as the host uploads it. A box's message occupies whole
+// 16-byte slots of the packed buffers: src_off and dst_off are multiples of
+// 16 and round_up(len, 16) bytes are read and written from them (what lies
+// past len is read, ignored, and written as zeros). The 16-byte tag sits right
+// in front of the ciphertext: at src_off - 16 of an open, at dst_off - 16 of a
+// seal. first_tile is the box's first 16 KiB tile of the launch
+// (xhip_k8_plan; xhip_k8_box_run sets it); the device copy of `key` is zeroed once the subkey exists.
+struct XhipBox {
+    uint32_t key[8];    // 32 bytes, little-endian words
+    uint32_t nonce[6];  // 24 bytes
+    uint32_t first_tile, reserved;
+    uint64_t src_off, dst_off, len, reserved2;  // 96 bytes
+};
+#define XHIP_K8_MAX_LEN (uint64_t(1) << 40)
+#define XHIP_K8_MAX_TILES 0x7fffffffu
+// The workspace of a batch: the boxes at 0, a key row per box at rows_off
+// (zeroed again by the last kernel), 32 bytes per tile at partials_off.
+struct XhipK8Plan {
+    uint32_t total_tiles;
+    uint64_t rows_off, partials_off, work_bytes;
+};
+// first_tile takes n_boxes + 1 entries, the last one the tile total.
+// hipErrorInvalidValue for a box above XHIP_K8_MAX_LEN bytes or a batch above
+// XHIP_K8_MAX_TILES tiles.
+hipError_t xhip_k8_plan(const uint64_t* lens, uint32_t n_boxes, uint32_t* first_tile,
+                        XhipK8Plan* plan);
+// mode 0 opens (src: tag || cipher, dst: plain, ok[i] = tag matched; the
+// output of a box that failed is zeroed on the device), 1 seals (src: plain,
+// dst: tag || cipher), 2 is Poly1305 alone (key = the one-time key, src: the
+// message, dst_off: where the 16-byte tag goes). host_boxes is host memory,
+// whose first_tile fields this call fills from the boxes' lengths; every
+// offset is checked against src_bytes / dst_bytes before any launch.
+hipError_t xhip_k8_box_run(int mode, XhipBox* host_boxes, uint32_t n_boxes, void* work,
+                           uint64_t work_bytes, const uint8_t* src, uint64_t src_bytes,
+                           uint8_t* dst, uint64_t dst_bytes, uint32_t* ok);
+
 }  // extern "C"

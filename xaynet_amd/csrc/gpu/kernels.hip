@@ -35,6 +35,7 @@
 // kernels; the f32 and i64 Bmax configs). Only f64 Bmax orders (2112..2143
 // bits) take the CPU oracle.
 #include "kernels.h"
+#include "box_stream.h"  // after kernels.h: needs the HIP runtime declared
 #include "mask_quant.h"
 #include "model_codec.h"
 #include "u192.h"
@@ -2879,4 +2880,279 @@ hipError_t xhip_k7r_emit(const uint64_t* planes, const uint64_t* mask_lo, const 
                            reinterpret_cast<uint32_t*>(out), out_bytes / 4);
         return hipGetLastError();
     });
+}
+
+// ------------------------------------- K8: batched XSalsa20-Poly1305 boxes
+//
+// M independent boxes in one packed buffer, cut into tiles of K8_BLOCK Salsa
+// blocks in stream coordinates (box_stream.h, where the arithmetic lives).
+// Three launches: k8_box_keys (per box: subkey, s, r^(2^m)), k8_box_stream
+// (per tile: keystream, XOR, Poly1305 partial, one pass over the bytes),
+// k8_box_finish (per box: combine the partials, tag, compare). An open is
+// followed by k8_box_wipe, which zeroes the output of every box whose tag
+// failed: stream has already written it, the caller must never see it.
+
+#define K8_BLOCK 256             // Salsa blocks, and threads, per tile
+#define K8_SLOTS (4 * K8_BLOCK)  // 16-byte slots per tile
+static_assert(K8_SLOTS < (1 << BS_POWERS), "r^(nb) is built from r^(2^m), m < BS_POWERS");
+static_assert(sizeof(XhipBox) % 16 == 0 && sizeof(bs_box_keys) % 16 == 0, "16-byte rows");
+
+// the box of global tile `tile`: the last one whose first_tile is not above it
+__device__ __forceinline__ uint32_t k8_find_box(const XhipBox* __restrict__ boxes, uint32_t n,
+                                                uint32_t tile) {
+    uint32_t lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (boxes[mid].first_tile <= tile)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ bs_fe k8_shfl_down(const bs_fe& a, int delta) {
+    bs_fe o;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) o.v[i] = __shfl_down(a.v[i], delta, WAVE);
+    return o;
+}
+
+// Six tree levels inside a wave, level m by pw[m]: lane 0 ends with
+// sum_l acc_l * pw[0]^(63 - l). Lanes whose partner lies outside the wave
+// compute values nobody reads.
+__device__ __forceinline__ bs_fe k8_wave_tree(bs_fe acc, const bs_fe* __restrict__ pw) {
+#pragma unroll
+    for (int m = 0; m < 6; ++m) acc = bs_step(acc, pw[m], k8_shfl_down(acc, 1 << m));
+    return acc;
+}
+
+// One lane per box: the serial part. Zeroes the descriptor's key behind it.
+template <bool MAC>
+__global__ void __launch_bounds__(WAVE) k8_box_keys(XhipBox* __restrict__ boxes,
+                                                    bs_box_keys* __restrict__ rows, uint32_t n) {
+    const uint32_t b = blockIdx.x * WAVE + threadIdx.x;
+    if (b >= n) return;
+    uint32_t key[8], nonce[6];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) key[i] = boxes[b].key[i];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) nonce[i] = boxes[b].nonce[i];
+    if (MAC)
+        bs_mac_keys_derive(rows[b], key);
+    else
+        bs_box_keys_derive(rows[b], key, nonce);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) boxes[b].key[i] = 0;
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(K8_BLOCK) k8_box_stream(
+    const XhipBox* __restrict__ boxes, const bs_box_keys* __restrict__ rows, uint32_t n_boxes,
+    const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, uint32_t* __restrict__ partials) {
+    __shared__ u32x4 ks_lds[MODE == BS_MAC ? 1 : K8_SLOTS];
+    __shared__ bs_fe wave_acc[K8_BLOCK / WAVE];
+    const uint32_t t = threadIdx.x;
+    const uint32_t b = k8_find_box(boxes, n_boxes, blockIdx.x);
+    const XhipBox& box = boxes[b];
+    const bs_box_keys& row = rows[b];
+    const uint64_t tile = blockIdx.x - box.first_tile, len = box.len;
+    const bs_tile_geo g = bs_geo(len, tile, K8_SLOTS);
+
+    if (MODE != BS_MAC) {
+        // thread t: Salsa block tile * 256 + t in registers, then to LDS
+        uint32_t key[8], ks[16];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) key[i] = row.subkey[i];
+        const uint32_t nonce8[2] = {box.nonce[4], box.nonce[5]};
+        bs_salsa_block(ks, key, nonce8, tile * K8_BLOCK + t);
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j)
+            ks_lds[bs_swizzle(4 * t + j)] =
+                u32x4{ks[4 * j], ks[4 * j + 1], ks[4 * j + 2], ks[4 * j + 3]};
+        __syncthreads();
+    }
+
+    // four passes, lane stride 16 bytes; Horner by r^256 over the lane's blocks
+    const bs_fe r_block = row.pw[8];
+    const u32x4* in = reinterpret_cast<const u32x4*>(src + box.src_off);
+    u32x4* out = reinterpret_cast<u32x4*>(dst + box.dst_off);
+    bs_fe acc = bs_fe_zero();
+#pragma unroll
+    for (uint32_t p = 0; p < 4; ++p) {
+        const uint32_t pos = p * K8_BLOCK + t;
+        uint64_t off;
+        const uint32_t bytes = bs_position(len, tile, K8_SLOTS, g, pos, &off);
+        uint32_t c[4] = {0, 0, 0, 0};
+        if (bytes) {
+            const u32x4 w = in[off / 16];
+            uint32_t x[4] = {w.x, w.y, w.z, w.w};
+            if (MODE != BS_MAC) {
+                const u32x4 k = ks_lds[bs_swizzle(pos - g.shift)];
+                uint32_t y[4] = {w.x ^ k.x, w.y ^ k.y, w.z ^ k.z, w.w ^ k.w};
+                bs_keep_bytes(y, bytes);
+                out[off / 16] = u32x4{y[0], y[1], y[2], y[3]};
+                if (MODE == BS_SEAL)
+                    for (int i = 0; i < 4; ++i) x[i] = y[i];
+            }
+            bs_keep_bytes(x, bytes);
+            for (int i = 0; i < 4; ++i) c[i] = x[i];
+        }
+        acc = bs_step(acc, r_block, bs_block(c, bytes));
+    }
+
+    // 256 lane accumulators -> one partial: a tree in each wave, Horner by
+    // r^64 over the four waves, and the last block's exponent 1
+    acc = k8_wave_tree(acc, row.pw);
+    if (t % WAVE == 0) wave_acc[t / WAVE] = acc;
+    __syncthreads();
+    if (t == 0) {
+        bs_fe h = wave_acc[0];
+        for (int w = 1; w < K8_BLOCK / WAVE; ++w) h = bs_step(h, row.pw[6], wave_acc[w]);
+        h = bs_mulmod(h, row.pw[0]);
+        uint32_t* P = partials + 8 * uint64_t(blockIdx.x);
+#pragma unroll
+        for (int i = 0; i < 5; ++i) P[i] = h.v[i];
+    }
+}
+
+// One wave per box.
+template <int MODE>
+__global__ void __launch_bounds__(WAVE) k8_box_finish(
+    XhipBox* __restrict__ boxes, bs_box_keys* __restrict__ rows,
+    const uint32_t* __restrict__ partials, const uint8_t* __restrict__ src,
+    uint8_t* __restrict__ dst, uint32_t* __restrict__ ok) {
+    const uint32_t b = blockIdx.x, l = threadIdx.x;
+    const XhipBox& box = boxes[b];
+    bs_box_keys& row = rows[b];
+    const uint64_t T = bs_tiles(box.len, K8_SLOTS), N = T - 1;
+    const uint32_t* P = partials + 8 * uint64_t(box.first_tile);
+
+    bs_fe xp[7];  // (r^1024)^(2^m)
+    xp[0] = row.pw[10];
+#pragma unroll
+    for (int m = 1; m < 7; ++m) xp[m] = bs_mulmod(xp[m - 1], xp[m - 1]);
+    // tiles 0..T-2, right-aligned on the lanes: `lead` empty positions first
+    const uint64_t lead = (BS_FINISH_LANES - N % BS_FINISH_LANES) % BS_FINISH_LANES;
+    bs_fe acc = bs_fe_zero();
+#pragma unroll 1
+    for (uint64_t u = l; u < N + lead; u += BS_FINISH_LANES) {
+        bs_fe add = bs_fe_zero();
+        if (u >= lead) {
+#pragma unroll
+            for (int i = 0; i < 5; ++i) add.v[i] = P[8 * (u - lead) + i];
+        }
+        acc = bs_step(acc, xp[6], add);
+    }
+    acc = k8_wave_tree(acc, xp);
+    if (l == 0) {
+        bs_fe last;
+#pragma unroll
+        for (int i = 0; i < 5; ++i) last.v[i] = P[8 * N + i];
+        const bs_fe h = bs_step(acc, bs_power(row.pw, bs_geo(box.len, N, K8_SLOTS).nb), last);
+        uint32_t tag[4];
+        bs_finish(tag, h, row.s);
+        if (MODE == BS_OPEN) {
+            const u32x4 given = *reinterpret_cast<const u32x4*>(src + box.src_off - 16);
+            const uint32_t gw[4] = {given.x, given.y, given.z, given.w};
+            ok[b] = bs_equal16(tag, gw) ? 1u : 0u;
+        } else {
+            uint8_t* at = MODE == BS_SEAL ? dst + box.dst_off - 16 : dst + box.dst_off;
+            *reinterpret_cast<u32x4*>(at) = u32x4{tag[0], tag[1], tag[2], tag[3]};
+            ok[b] = 1u;
+        }
+    }
+    __syncthreads();
+    // the key material has done its work
+    uint32_t* words = reinterpret_cast<uint32_t*>(&row);
+    for (uint32_t i = l; i < sizeof(bs_box_keys) / 4; i += WAVE) words[i] = 0;
+}
+
+// After an open: zero the output of every box whose tag failed, tile by tile.
+__global__ void __launch_bounds__(K8_BLOCK) k8_box_wipe(const XhipBox* __restrict__ boxes,
+                                                        uint32_t n_boxes,
+                                                        const uint32_t* __restrict__ ok,
+                                                        uint8_t* __restrict__ dst) {
+    const uint32_t b = k8_find_box(boxes, n_boxes, blockIdx.x);
+    if (ok[b]) return;
+    const XhipBox& box = boxes[b];
+    const uint64_t tile = blockIdx.x - box.first_tile;
+    const bs_tile_geo g = bs_geo(box.len, tile, K8_SLOTS);
+    u32x4* out = reinterpret_cast<u32x4*>(dst + box.dst_off);
+    for (uint32_t p = 0; p < 4; ++p) {
+        uint64_t off;
+        if (bs_position(box.len, tile, K8_SLOTS, g, p * K8_BLOCK + threadIdx.x, &off))
+            out[off / 16] = u32x4{0, 0, 0, 0};
+    }
+}
+
+static uint64_t k8_round_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
+
+hipError_t xhip_k8_plan(const uint64_t* lens, uint32_t n_boxes, uint32_t* first_tile,
+                        XhipK8Plan* plan) {
+    *plan = XhipK8Plan{};
+    uint64_t tiles = 0;
+    for (uint32_t i = 0; i < n_boxes; ++i) {
+        if (lens[i] > XHIP_K8_MAX_LEN) return hipErrorInvalidValue;
+        first_tile[i] = uint32_t(tiles);
+        tiles += bs_tiles(lens[i], K8_SLOTS);
+        if (tiles > XHIP_K8_MAX_TILES) return hipErrorInvalidValue;
+    }
+    first_tile[n_boxes] = uint32_t(tiles);
+    plan->total_tiles = uint32_t(tiles);
+    plan->rows_off = k8_round_up(sizeof(XhipBox) * uint64_t(n_boxes), 64);
+    plan->partials_off = k8_round_up(plan->rows_off + sizeof(bs_box_keys) * uint64_t(n_boxes), 64);
+    plan->work_bytes = plan->partials_off + 32 * tiles;
+    return hipSuccess;
+}
+
+hipError_t xhip_k8_box_run(int mode, XhipBox* host_boxes, uint32_t n_boxes, void* work,
+                           uint64_t work_bytes, const uint8_t* src, uint64_t src_bytes,
+                           uint8_t* dst, uint64_t dst_bytes, uint32_t* ok) {
+    if (mode != BS_OPEN && mode != BS_SEAL && mode != BS_MAC) return hipErrorInvalidValue;
+    if (n_boxes == 0) return hipSuccess;
+    if (!host_boxes || !work || !src || !dst || !ok || reinterpret_cast<uintptr_t>(work) % 16 ||
+        reinterpret_cast<uintptr_t>(src) % 16 || reinterpret_cast<uintptr_t>(dst) % 16)
+        return hipErrorInvalidValue;
+    // every byte the kernels touch, checked here: whole 16-byte slots of the
+    // message in src (and dst), the tag in front of it (at dst_off for a MAC)
+    std::vector<uint64_t> lens(n_boxes);
+    for (uint32_t i = 0; i < n_boxes; ++i) lens[i] = host_boxes[i].len;
+    std::vector<uint32_t> first(n_boxes + 1);
+    XhipK8Plan plan;
+    hipError_t e = xhip_k8_plan(lens.data(), n_boxes, first.data(), &plan);
+    if (e != hipSuccess) return e;
+    if (work_bytes < plan.work_bytes) return hipErrorInvalidValue;
+    for (uint32_t i = 0; i < n_boxes; ++i) {
+        XhipBox& x = host_boxes[i];
+        x.first_tile = first[i];
+        const uint64_t span = k8_round_up(x.len, 16);
+        const uint64_t src_front = mode == BS_OPEN ? 16 : 0, dst_front = mode == BS_SEAL ? 16 : 0;
+        const uint64_t dst_span = mode == BS_MAC ? 16 : span;
+        if (x.src_off % 16 || x.dst_off % 16 ||
+            x.src_off < src_front || x.src_off > src_bytes || span > src_bytes - x.src_off ||
+            x.dst_off < dst_front || x.dst_off > dst_bytes || dst_span > dst_bytes - x.dst_off)
+            return hipErrorInvalidValue;
+    }
+    uint8_t* base = static_cast<uint8_t*>(work);
+    XhipBox* boxes = reinterpret_cast<XhipBox*>(base);
+    bs_box_keys* rows = reinterpret_cast<bs_box_keys*>(base + plan.rows_off);
+    uint32_t* partials = reinterpret_cast<uint32_t*>(base + plan.partials_off);
+    e = hipMemcpy(boxes, host_boxes, sizeof(XhipBox) * uint64_t(n_boxes), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return e;
+    const dim3 per_box((n_boxes + WAVE - 1) / WAVE), tiles(plan.total_tiles);
+    auto run = [&](auto m) {
+        constexpr int MODE = decltype(m)::value;
+        hipLaunchKernelGGL(k8_box_keys<MODE == BS_MAC>, per_box, dim3(WAVE), 0, 0, boxes, rows, n_boxes);
+        hipLaunchKernelGGL(k8_box_stream<MODE>, tiles, dim3(K8_BLOCK), 0, 0, boxes, rows, n_boxes,
+                           src, dst, partials);
+        hipLaunchKernelGGL(k8_box_finish<MODE>, dim3(n_boxes), dim3(WAVE), 0, 0, boxes, rows,
+                           partials, src, dst, ok);
+        if (MODE == BS_OPEN)
+            hipLaunchKernelGGL(k8_box_wipe, tiles, dim3(K8_BLOCK), 0, 0, boxes, n_boxes, ok, dst);
+        return hipGetLastError();
+    };
+    if (mode == BS_OPEN) return run(std::integral_constant<int, BS_OPEN>{});
+    if (mode == BS_SEAL) return run(std::integral_constant<int, BS_SEAL>{});
+    return run(std::integral_constant<int, BS_MAC>{});
 }

@@ -1,3 +1,4 @@
+from .box import GpuBox  # noqa: F401
 from .engine import GpuMaskedAggregator, gpu_available  # noqa: F401
 
 

@@ -1,0 +1,221 @@
+"""Batched NaCl boxes on the GPU (K8): XSalsa20-Poly1305 over many
+independent messages in one launch, byte for byte what `_core.crypto` (and
+libsodium) produce.
+
+A batch lives in one packed device buffer. Every box gets `_HEAD` bytes of
+head room and its message starts on a 64-byte boundary, so the kernels' 16-byte
+accesses are aligned, the tag (and a sealed box's ephemeral key) sit right in
+front of the ciphertext, and an opened payload is a 16-byte-aligned view that a
+later kernel can read in place. X25519 and the sealed-box nonce (blake2b) stay
+on the host; only the bulk pass over the bytes runs on the device.
+
+The kernels decrypt and authenticate in one pass, so plaintext of a forged
+box does exist in the output buffer for a moment: a last kernel zeroes it, and
+this layer hands out `None` for it. Nothing here returns a view of a box whose
+tag failed.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from xaynet_amd import _core
+
+from .engine import _hip, _require_gpu
+
+_OPEN, _SEAL, _MAC = 0, 1, 2
+_HEAD = 64  # bytes in front of every message: room for epk(32) || tag(16)
+_crypto = _core.crypto
+
+
+def _nbytes(item):
+    """Bytes of a host buffer or a device tensor of any dtype."""
+    if isinstance(item, torch.Tensor):
+        return item.numel() * item.element_size()
+    return memoryview(item).nbytes
+
+
+def _as_bytes(t):
+    """A device tensor of any dtype as a flat uint8 tensor."""
+    return t.contiguous().view(torch.uint8).reshape(-1)
+
+
+def _layout(lens):
+    """Message offsets of a batch and the packed buffer's size."""
+    offs, at = [], 0
+    for n in lens:
+        offs.append(at + _HEAD)
+        at += _HEAD + (n + 63) // 64 * 64
+    return offs, at + _HEAD
+
+
+class GpuBox:
+    """Seal and open batches of boxes on one GPU. `kernel_ms` is the device
+    time of the last batch's kernels when `time_kernels` is set. After an
+    open, `opened_buffer` is the packed uint8 device buffer the returned views
+    lie in and `opened_offsets[i]` the byte offset of box i's payload in it
+    (a multiple of 16; None for a box shorter than a tag): the payload of a
+    box that failed is zeros there."""
+
+    def __init__(self, device: str = "cuda:0", time_kernels: bool = False):
+        _require_gpu()
+        self.device = torch.device(device)
+        self.time_kernels = time_kernels
+        self.kernel_ms = None
+        self._pin = None  # pinned staging buffer, grown on demand, wiped after a seal
+        self.opened_buffer = self.opened_offsets = None
+        self._work = None
+
+    # ---------------- packing ----------------
+
+    def _new(self, nbytes):
+        return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.device)
+
+    def _pack(self, items, offs, front, total, wipe=False):
+        """The items (host buffers or device tensors) in one device buffer,
+        item i starting `front` bytes before offs[i]. Host items go through
+        one pinned staging buffer and one copy; `wipe` zeroes what they left
+        there (plaintext on its way to a seal) once it is on the device."""
+        buf = self._new(total)
+        host = [i for i, it in enumerate(items) if not isinstance(it, torch.Tensor)]
+        if host:
+            if self._pin is None or self._pin.numel() < total:
+                self._pin = torch.empty(total, dtype=torch.uint8).pin_memory()
+            stage = self._pin.numpy()
+            for i in host:
+                view = np.frombuffer(memoryview(items[i]).cast("B"), dtype=np.uint8)
+                stage[offs[i] - front:offs[i] - front + view.size] = view
+            if len(host) == len(items):
+                buf.copy_(self._pin[:total])
+            else:
+                for i in host:
+                    a, b = offs[i] - front, offs[i] - front + _nbytes(items[i])
+                    buf[a:b].copy_(self._pin[a:b])
+            if wipe:  # the copies above block until the bytes have left
+                self._pin[:total].zero_()
+        for i, it in enumerate(items):
+            if isinstance(it, torch.Tensor):
+                flat = _as_bytes(it.to(self.device))
+                buf[offs[i] - front:offs[i] - front + flat.numel()].copy_(flat)
+        return buf
+
+    def _run(self, mode, lens, keys, nonces, src, src_offs, dst, dst_offs):
+        keys = [bytes(k) for k in keys]
+        nonces = [bytes(n) for n in nonces]
+        if len(keys) != len(lens) or any(len(k) != 32 for k in keys):
+            raise ValueError("one 32-byte key a box")
+        if mode != _MAC and (len(nonces) != len(lens) or any(len(n) != 24 for n in nonces)):
+            raise ValueError("one 24-byte nonce a box")
+        with torch.cuda.device(self.device):
+            _, work_bytes = _hip._box_plan(lens)
+            if self._work is None or self._work.numel() < work_bytes:
+                self._work = self._new(work_bytes)
+            ok = torch.empty(len(lens), dtype=torch.int32, device=self.device)
+            if self.time_kernels:
+                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0.record()
+            _hip._box_run(mode, b"".join(keys), b"".join(nonces), lens, src_offs, dst_offs,
+                          src.data_ptr(), src.numel(), dst.data_ptr(), dst.numel(),
+                          self._work.data_ptr(), self._work.numel(), ok.data_ptr())
+            if self.time_kernels:
+                t1.record()
+                t1.synchronize()
+                self.kernel_ms = t0.elapsed_time(t1)
+        return ok
+
+    # ---------------- secretbox ----------------
+
+    def secretbox_open_batch(self, boxes, keys, nonces):
+        """Open tag || cipher boxes. Returns (messages, ok): message i is a
+        uint8 device view into one packed buffer, or None where the tag failed
+        (or the box is shorter than a tag); ok is the device bool tensor."""
+        n = len(boxes)
+        live = [i for i in range(n) if _nbytes(boxes[i]) >= 16]
+        ok = torch.zeros(n, dtype=torch.bool, device=self.device)
+        out = [None] * n
+        self.opened_buffer, self.opened_offsets = None, [None] * n
+        if not live:
+            return out, ok
+        lens = [_nbytes(boxes[i]) - 16 for i in live]
+        offs, total = _layout(lens)
+        src = self._pack([boxes[i] for i in live], offs, 16, total)
+        dst = self._new(total)
+        good = self._run(_OPEN, lens, [keys[i] for i in live], [nonces[i] for i in live], src,
+                         offs, dst, offs).bool()
+        ok[torch.tensor(live, device=self.device)] = good
+        self.opened_buffer = dst
+        for i, off, m, g in zip(live, offs, lens, good.tolist()):
+            self.opened_offsets[i] = off
+            if g:
+                out[i] = dst[off:off + m]
+        return out, ok
+
+    def _seal(self, messages, keys, nonces, heads=None):
+        lens = [_nbytes(m) for m in messages]
+        offs, total = _layout(lens)
+        src = self._pack(messages, offs, 0, total, wipe=True)
+        dst = self._new(total)
+        self._run(_SEAL, lens, keys, nonces, src, offs, dst, offs)
+        front = 16
+        if heads is not None:  # epk in front of every tag
+            front = 48
+            at = torch.tensor(offs, device=self.device)[:, None] - 48 + \
+                torch.arange(32, device=self.device)
+            epk = torch.frombuffer(bytearray(b"".join(heads)), dtype=torch.uint8)
+            dst[at.reshape(-1)] = epk.to(self.device)
+        return [dst[off - front:off + m] for off, m in zip(offs, lens)]
+
+    def secretbox_seal_batch(self, messages, keys, nonces):
+        """Seal host buffers or device tensors; returns uint8 device tensors
+        tag || cipher, views into one packed buffer."""
+        if not len(messages):
+            return []
+        return self._seal(messages, keys, nonces)
+
+    # ---------------- sealed boxes ----------------
+
+    def sealbox_open_batch(self, sealed, pk, sk):
+        """Open epk || tag || cipher sealed boxes addressed to (pk, sk): as
+        secretbox_open_batch, with the key agreement per box on the host."""
+        pk, sk = bytes(pk), bytes(sk)
+        boxes, keys, nonces = [], [], []
+        for s in sealed:
+            if isinstance(s, torch.Tensor):
+                s = _as_bytes(s)
+            if _nbytes(s) < 48:
+                boxes.append(b"")
+                keys.append(bytes(32))
+                nonces.append(bytes(24))
+                continue
+            epk = bytes(s[:32].cpu().numpy()) if isinstance(s, torch.Tensor) else \
+                bytes(memoryview(s).cast("B")[:32])
+            boxes.append(s[32:] if isinstance(s, torch.Tensor) else memoryview(s).cast("B")[32:])
+            keys.append(_crypto.box_beforenm(epk, sk))
+            nonces.append(_crypto.blake2b(epk + pk, 24))
+        return self.secretbox_open_batch(boxes, keys, nonces)
+
+    def sealbox_seal_batch(self, messages, pk):
+        """Seal to pk with a fresh ephemeral key per message; returns uint8
+        device tensors epk || tag || cipher."""
+        if not len(messages):
+            return []
+        pk = bytes(pk)
+        heads, keys, nonces = [], [], []
+        for _ in messages:
+            epk, esk = _crypto.box_keypair()
+            heads.append(epk)
+            keys.append(_crypto.box_beforenm(pk, esk))
+            nonces.append(_crypto.blake2b(epk + pk, 24))
+        return self._seal(messages, keys, nonces, heads)
+
+    # ---------------- the MAC alone ----------------
+
+    def poly1305(self, data, key32) -> bytes:
+        """Poly1305 of `data` under the one-time key through the tile and
+        finish kernels; the 16-byte tag."""
+        n = _nbytes(data)
+        offs, total = _layout([n])
+        src = self._pack([data], offs, 0, total)
+        tag = self._new(16)
+        self._run(_MAC, [n], [key32], [], src, offs, tag, [0])
+        return bytes(tag.cpu().numpy())
