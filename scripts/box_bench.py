@@ -14,7 +14,17 @@ Per shape and direction, after one warm-up call:
 Opened and sealed bytes are compared with the CPU's before anything is timed.
 One JSON line per shape and direction.
 
+--device-keys measures K9 instead: per shape (default 4096 x 4 KiB and the seed
+dicts 1024 x 32 B and 10240 x 32 B) and direction, `device_keys=True` (X25519,
+key and nonce on the device), `device_keys=False` (the ladders on the host) and
+the CPU box are taken alternately, --reps rounds, after a warm-up call that
+compares every byte; medians with min..max. --seed-sweep times
+GpuBox.open_seeds / seal_seed (host bytes in and out) against the CPU loop over
+batch sizes, which is what GpuBox.SEEDS_MIN_BATCH is read from, and
+x25519_batch against `_core.crypto.x25519`.
+
 Usage (GPU box): python scripts/box_bench.py [--reps 5] [--shapes 1x175000000,64x8388608]
+                 python scripts/box_bench.py --device-keys [--seed-sweep]
 """
 import argparse
 import json
@@ -46,11 +56,84 @@ def timed(fn, reps):
     return walls
 
 
+def spread(v):
+    return {"median": round(statistics.median(v), 3), "min_max": [round(min(v), 3),
+                                                                  round(max(v), 3)]}
+
+
+def device_keys_bench(args):
+    box = GpuBox("cuda:0", time_kernels=True)
+    pk, sk = cr.box_seed_keypair(b"\x42" * 32)
+    rng = np.random.default_rng(19)
+    for shape in (args.shapes or "4096x4096,1024x32,10240x32").split(","):
+        count, size = (int(x) for x in shape.split("x"))
+        msgs = [rng.bytes(size) for _ in range(count)]
+        sealed = [bytes(cr.sealbox_seal(m, pk)) for m in msgs]
+        # warm-up, every byte compared
+        opened, ok = box.sealbox_open_batch(sealed, pk, sk, device_keys=True)
+        assert bool(ok.all()) and all(bytes(t.cpu().numpy()) == m for t, m in zip(opened, msgs))
+        resealed = box.sealbox_seal_batch(msgs, pk, device_keys=True)
+        assert all(cr.sealbox_open(bytes(t.cpu().numpy()), pk, sk) == m
+                   for t, m in zip(resealed, msgs))
+        box.sealbox_open_batch(sealed, pk, sk)
+        box.sealbox_seal_batch(msgs, pk)
+        del opened, resealed
+        for name, gpu, cpu in (
+            ("open", lambda dk: box.sealbox_open_batch(sealed, pk, sk, device_keys=dk),
+             lambda: [cr.sealbox_open(s, pk, sk) for s in sealed]),
+            ("seal", lambda dk: box.sealbox_seal_batch(msgs, pk, device_keys=dk),
+             lambda: [cr.sealbox_seal(m, pk) for m in msgs]),
+        ):
+            t = {"dev_kernel": [], "dev_call": [], "host_kernel": [], "host_call": [], "cpu": []}
+            for _ in range(args.reps):
+                t["dev_call"] += timed(lambda: gpu(True), 1)
+                t["dev_kernel"].append(box.kernel_ms)
+                t["host_call"] += timed(lambda: gpu(False), 1)
+                t["host_kernel"].append(box.kernel_ms)
+                t["cpu"] += timed(cpu, 1)
+            print(json.dumps({"op": name, "boxes": count, "bytes_per_box": size,
+                              "reps": args.reps,
+                              "device_keys_kernel_ms": spread(t["dev_kernel"]),
+                              "device_keys_call_ms": spread(t["dev_call"]),
+                              "host_keys_kernel_ms": spread(t["host_kernel"]),
+                              "host_keys_call_ms": spread(t["host_call"]),
+                              "cpu_ms_one_thread": spread(t["cpu"])}), flush=True)
+    if not args.seed_sweep:
+        return
+    GpuBox.SEEDS_MIN_BATCH = 0
+    for n in (4, 16, 64, 256, 1024, 4096, 16384, 65536):
+        seeds = [rng.bytes(32) for _ in range(n)]
+        enc = [bytes(cr.sealbox_seal(s, pk)) for s in seeds]
+        pks = [cr.x25519_base(s) for s in seeds]
+        assert box.open_seeds(enc, pk, sk) == seeds
+        assert box.x25519_batch(seeds[:64], pks[:64]) == \
+            [cr.x25519(a, b) for a, b in zip(seeds[:64], pks[:64])]
+        box.seal_seed(seeds[0], pks)
+        t = {"open_gpu": [], "open_cpu": [], "seal_gpu": [], "seal_cpu": [], "x25519_gpu": [],
+             "x25519_cpu": []}
+        for _ in range(args.reps):
+            t["open_gpu"] += timed(lambda: box.open_seeds(enc, pk, sk), 1)
+            t["open_cpu"] += timed(lambda: [cr.sealbox_open(e, pk, sk) for e in enc], 1)
+            t["seal_gpu"] += timed(lambda: box.seal_seed(seeds[0], pks), 1)
+            t["seal_cpu"] += timed(lambda: [cr.sealbox_seal(seeds[0], k) for k in pks], 1)
+            t["x25519_gpu"] += timed(lambda: box.x25519_batch(seeds, pks), 1)
+            if n <= 4096:
+                t["x25519_cpu"] += timed(lambda: [cr.x25519(a, b) for a, b in zip(seeds, pks)],
+                                         1)
+        print(json.dumps({"seeds": n, "reps": args.reps,
+                          **{k + "_ms": spread(v) for k, v in t.items() if v}}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--shapes", default="1x175000000,64x8388608,4096x4096")
+    ap.add_argument("--shapes", default=None)
+    ap.add_argument("--device-keys", action="store_true")
+    ap.add_argument("--seed-sweep", action="store_true")
     args = ap.parse_args()
+    if args.device_keys:
+        return device_keys_bench(args)
+    args.shapes = args.shapes or "1x175000000,64x8388608,4096x4096"
 
     box = GpuBox("cuda:0", time_kernels=True)
     pk, sk = cr.box_seed_keypair(b"\x42" * 32)

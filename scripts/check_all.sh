@@ -36,6 +36,10 @@ build/model_encode_ratio_sanitize
 g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
     -Ixaynet_amd/csrc scripts/unmask_round_sanitize.cpp -o build/unmask_round_sanitize
 build/unmask_round_sanitize
+# the K9 ladder, field arithmetic and sealed-box nonce (fe25519.h) over the edge points
+g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
+    -Ixaynet_amd/csrc scripts/x25519_sanitize.cpp -o build/x25519_sanitize
+build/x25519_sanitize
 bash scripts/sanitize.sh
 bash scripts/tsan.sh
 

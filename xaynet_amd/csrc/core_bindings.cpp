@@ -17,6 +17,7 @@
 #include "crypto/poly1305.h"
 #include "crypto/sha2.h"
 #include "gpu/box_stream.h"
+#include "gpu/fe25519.h"
 
 namespace py = pybind11;
 using namespace xaynet;
@@ -215,10 +216,56 @@ PYBIND11_MODULE(_core, m) {
         },
         py::arg("mode"), py::arg("data"), py::arg("nonce"), py::arg("key"),
         py::arg("tile_blocks"));
+    // The GPU ladder and sealed-box nonce (gpu/fe25519.h) on the host: what
+    // the K9 kernels compute, for tests without a device.
+    c.def("x25519_host", [](py::bytes scalar, py::bytes point) {
+        Bytes s = from_pybytes(scalar), p = from_pybytes(point);
+        if (s.size() != 32 || p.size() != 32) throw py::value_error("scalar and point are 32 bytes");
+        uint32_t sw[8], pw[8], out[8];
+        std::memcpy(sw, s.data(), 32);
+        std::memcpy(pw, p.data(), 32);
+        fe_x25519(out, sw, pw);
+        return to_pybytes(reinterpret_cast<const uint8_t*>(out), 32);
+    });
+    c.def("seal_nonce_host", [](py::bytes epk, py::bytes pk) {
+        Bytes e = from_pybytes(epk), p = from_pybytes(pk);
+        if (e.size() != 32 || p.size() != 32) throw py::value_error("keys are 32 bytes");
+        uint32_t ew[8], pw[8], out[6];
+        std::memcpy(ew, e.data(), 32);
+        std::memcpy(pw, p.data(), 32);
+        fe_seal_nonce(out, ew, pw);
+        return to_pybytes(reinterpret_cast<const uint8_t*>(out), 24);
+    });
+    // What k9_box_agree makes of a ladder output: HSalsa20(X25519(sk, epk), 0),
+    // the value of box_beforenm(epk, sk).
+    c.def("box_key_host", [](py::bytes epk, py::bytes sk) {
+        Bytes e = from_pybytes(epk), s = from_pybytes(sk);
+        if (e.size() != 32 || s.size() != 32) throw py::value_error("keys are 32 bytes");
+        uint32_t ew[8], sw[8], shared[8], key[8];
+        const uint32_t zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        std::memcpy(ew, e.data(), 32);
+        std::memcpy(sw, s.data(), 32);
+        fe_x25519(shared, sw, ew);
+        bs_hsalsa(key, shared, zero);
+        return to_pybytes(reinterpret_cast<const uint8_t*>(key), 32);
+    });
     c.def("randombytes", [](size_t n) {
         Bytes out(n);
         randombytes(out.data(), n);
         return to_pybytes(out.data(), n);
+    });
+    // Random bytes straight into a writable byte buffer of one or two
+    // dimensions with contiguous rows (a strided view of a pinned staging
+    // buffer): secrets that are never a Python object.
+    c.def("randombytes_into", [](py::buffer out) {
+        py::buffer_info bi = out.request(true);
+        if (bi.itemsize != 1 || bi.ndim < 1 || bi.ndim > 2 || bi.strides[bi.ndim - 1] != 1)
+            throw py::value_error("a writable byte buffer of one or two dimensions, its rows "
+                                  "contiguous");
+        const py::ssize_t rows = bi.ndim == 2 ? bi.shape[0] : 1, width = bi.shape[bi.ndim - 1];
+        for (py::ssize_t r = 0; r < rows; ++r)
+            randombytes(static_cast<uint8_t*>(bi.ptr) + (bi.ndim == 2 ? r * bi.strides[0] : 0),
+                        size_t(width));
     });
     c.def("is_eligible", [](py::bytes sig, double threshold) {
         // int(sha256(sig) as LE) / (2^256 - 1) <= threshold

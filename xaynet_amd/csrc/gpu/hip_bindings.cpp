@@ -11,6 +11,7 @@
 #include <cstring>
 #include <stdexcept>
 #include <string>
+#include <string_view>
 #include <utility>
 #include <vector>
 
@@ -100,6 +101,15 @@ static long double limbs_to_ld(const Limbs& a) {
 
 static uint64_t* u64p(uintptr_t p) { return reinterpret_cast<uint64_t*>(p); }
 static uint8_t* u8p(uintptr_t p) { return reinterpret_cast<uint8_t*>(p); }
+
+// zero a host copy of key material: stores the compiler may not drop
+static void wipe(void* p, uint64_t n) {
+    volatile uint8_t* w = static_cast<volatile uint8_t*>(p);
+    for (uint64_t i = 0; i < n; ++i) w[i] = 0;
+}
+
+// K9 counts two ladders a box in 32 bits
+static constexpr size_t K9_MAX_BATCH = 0x3fffffffu;
 
 static void check(hipError_t e, const char* what) {
     if (e != hipSuccess) {
@@ -672,6 +682,124 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("src_offs"), py::arg("dst_offs"), py::arg("src"), py::arg("src_bytes"),
         py::arg("dst"), py::arg("dst_bytes"), py::arg("work"), py::arg("work_bytes"),
         py::arg("ok"));
+
+    // private (ops/box.py): K9 alone. scalars and points: 32 bytes a ladder,
+    // read in place; work: 64 bytes a ladder of device memory. Returns the
+    // 32-byte results, concatenated. Every copy of the scalars and results
+    // made here and on the device is overwritten.
+    m.def(
+        "_x25519_batch",
+        [](std::string_view scalars, std::string_view points, uintptr_t work,
+           uint64_t work_bytes) {
+            const size_t n = scalars.size() / 32;
+            if (scalars.size() != 32 * n || points.size() != 32 * n || n > K9_MAX_BATCH)
+                throw py::value_error("_x25519_batch: 32 scalar and 32 point bytes a ladder, "
+                                      "at most 2^30 - 1 ladders");
+            std::vector<XhipLadder> rows(n);
+            for (size_t i = 0; i < n; ++i) {
+                std::memcpy(rows[i].scalar, scalars.data() + 32 * i, 32);
+                std::memcpy(rows[i].point, points.data() + 32 * i, 32);
+            }
+            hipError_t e;
+            {
+                py::gil_scoped_release release;
+                e = xhip_k9_x25519_run(rows.data(), uint32_t(n), reinterpret_cast<void*>(work),
+                                       work_bytes);
+            }
+            std::string out(32 * n, '\0');
+            if (e == hipSuccess)
+                for (size_t i = 0; i < n; ++i) std::memcpy(&out[32 * i], rows[i].scalar, 32);
+            wipe(rows.data(), n * sizeof(XhipLadder));
+            py::bytes result(e == hipSuccess ? out : std::string());
+            wipe(out.data(), out.size());
+            if (e == hipErrorInvalidValue)
+                throw py::value_error("_x25519_batch: the workspace does not fit");
+            check(e, "k9_x25519_run");
+            return result;
+        },
+        py::arg("scalars"), py::arg("points"), py::arg("work"), py::arg("work_bytes"));
+
+    // private (ops/box.py): what _sealbox_run takes for a batch: the device
+    // workspace, the pinned upload buffer, and where in the latter the ladder
+    // rows (64 bytes each: scalar, point) begin
+    m.def(
+        "_sealbox_plan",
+        [](int mode, const std::vector<uint64_t>& lens) {
+            XhipK9Plan plan;
+            if (lens.size() > K9_MAX_BATCH ||
+                xhip_k9_plan(mode, lens.data(), uint32_t(lens.size()), &plan) != hipSuccess)
+                throw py::value_error("mode is 0 or 1; a box is at most 2^40 bytes, a batch "
+                                      "2^30 - 1 boxes and 2^31 - 1 tiles");
+            return py::make_tuple(plan.work_bytes, plan.upload_bytes, plan.ladders_off);
+        },
+        py::arg("mode"), py::arg("lens"));
+
+    // private (ops/box.py): K9 then K8 over one batch of sealed boxes, keys
+    // and nonces derived on the device. upload: pinned host memory of
+    // _sealbox_plan's size, which this call fills, sends in one copy and then
+    // zeroes, whatever the outcome. mode 0 opens: sk is the recipient's, pks its
+    // pk (32 bytes each), the ephemeral keys are read from src at src_off - 48.
+    // mode 1 seals: sk is empty and the caller has put one fresh esk a box into
+    // the scalar of ladder row i of upload (so that no other host copy of it
+    // exists), pks the recipients' (32 bytes, or 32 a box); epk || tag are
+    // written at dst_off - 48. The rest as _box_run.
+    m.def(
+        "_sealbox_run",
+        [](int mode, uintptr_t upload, uint64_t upload_bytes, std::string_view sk,
+           std::string_view pks, const std::vector<uint64_t>& lens,
+           const std::vector<uint64_t>& src_offs, const std::vector<uint64_t>& dst_offs,
+           uintptr_t src, uint64_t src_bytes, uintptr_t dst, uint64_t dst_bytes, uintptr_t work,
+           uint64_t work_bytes, uintptr_t ok) {
+            struct Wipe {  // the scalars' copy here goes as the device copy does
+                uint8_t* p;
+                uint64_t n;
+                ~Wipe() { wipe(p, n); }
+            } guard{reinterpret_cast<uint8_t*>(upload), upload ? upload_bytes : 0};
+            const size_t n = lens.size();
+            const bool one_pk = pks.size() == 32;
+            if ((mode != 0 && mode != 1) || sk.size() != (mode == 0 ? 32u : 0u) ||
+                (!one_pk && pks.size() != 32 * n) || src_offs.size() != n ||
+                dst_offs.size() != n || n > K9_MAX_BATCH)
+                throw py::value_error("_sealbox_run: mode 0 with a 32-byte sk or mode 1 with "
+                                      "none, 32 pk bytes (a box) and one offset pair a box");
+            XhipK9Plan plan;
+            if (xhip_k9_plan(mode, lens.data(), uint32_t(n), &plan) != hipSuccess)
+                throw py::value_error("a box is at most 2^40 bytes, a batch 2^31 - 1 tiles");
+            if (!upload || upload_bytes < plan.upload_bytes)
+                throw py::value_error("_sealbox_run: the upload buffer does not fit");
+            uint8_t* up = guard.p;
+            std::memset(up, 0, plan.ladders_off);
+            XhipBox* boxes = reinterpret_cast<XhipBox*>(up);
+            XhipLadder* rows = reinterpret_cast<XhipLadder*>(up + plan.ladders_off);
+            static const uint8_t base_point[32] = {9};
+            for (size_t i = 0; i < n; ++i) {
+                boxes[i].src_off = src_offs[i];
+                boxes[i].dst_off = dst_offs[i];
+                boxes[i].len = lens[i];
+                std::memcpy(rows[i].point, pks.data() + (one_pk ? 0 : 32 * i), 32);
+                if (mode == 0) {
+                    std::memcpy(rows[i].scalar, sk.data(), 32);
+                } else {
+                    std::memcpy(rows[n + i].scalar, rows[i].scalar, 32);
+                    std::memcpy(rows[n + i].point, base_point, 32);
+                }
+            }
+            hipError_t e;
+            {
+                py::gil_scoped_release release;
+                e = xhip_k9_sealbox_run(mode, up, uint32_t(n), reinterpret_cast<void*>(work),
+                                        work_bytes, u8p(src), src_bytes, u8p(dst), dst_bytes,
+                                        reinterpret_cast<uint32_t*>(ok));
+            }
+            if (e == hipErrorInvalidValue)
+                throw py::value_error("_sealbox_run: an offset, a length, the batch or the "
+                                      "workspace does not fit");
+            check(e, "k9_sealbox_run");
+        },
+        py::arg("mode"), py::arg("upload"), py::arg("upload_bytes"), py::arg("sk"),
+        py::arg("pks"), py::arg("lens"), py::arg("src_offs"), py::arg("dst_offs"),
+        py::arg("src"), py::arg("src_bytes"), py::arg("dst"), py::arg("dst_bytes"),
+        py::arg("work"), py::arg("work_bytes"), py::arg("ok"));
 
     // [n_planes][len] digit planes minus the mask -> model weights.
     // dtype follows mask::DataType: 0=F32 1=F64 2=I32 3=I64

@@ -341,4 +341,39 @@ hipError_t xhip_k8_box_run(int mode, XhipBox* host_boxes, uint32_t n_boxes, void
                            uint64_t work_bytes, const uint8_t* src, uint64_t src_bytes,
                            uint8_t* dst, uint64_t dst_bytes, uint32_t* ok);
 
+// ---- K9: batched X25519 and the sealed-box key agreement ----
+//
+// One ladder of a batch: out = X25519(scalar, point), 32 bytes each as
+// little-endian words. The kernel writes `out` over `scalar`, so no scalar
+// outlives its ladder on the device. No low-order-point rejection (fe25519.h).
+struct XhipLadder {
+    uint32_t scalar[8];  // in: the scalar (clamped by the kernel); out: the result
+    uint32_t point[8];   // the u coordinate; bit 255 ignored, values >= p accepted
+};  // 64 bytes
+// Uploads host_rows into work (64 bytes a row, 16-byte aligned device memory),
+// runs one ladder per lane and copies the rows back: host_rows[i].scalar is
+// then X25519 of row i.
+hipError_t xhip_k9_x25519_run(XhipLadder* host_rows, uint32_t n, void* work,
+                              uint64_t work_bytes);
+// The workspace of a sealed-box batch. The first upload_bytes are what the
+// host fills and the launcher uploads in one copy: the XhipBox descriptors at
+// 0 (keys and nonces zero: the device derives them) and the ladders at
+// ladders_off. An open has one ladder a box, (sk, pk): its point is read from
+// the box's ephemeral key in src, and `point` carries the recipient's pk for
+// the nonce. A seal has two: row i is (esk_i, pk_i), row n + i is (esk_i, 9).
+// Behind them the K8 key rows and tile partials.
+struct XhipK9Plan {
+    uint32_t ladders, total_tiles;
+    uint64_t ladders_off, upload_bytes, rows_off, partials_off, work_bytes;
+};
+hipError_t xhip_k9_plan(int mode, const uint64_t* lens, uint32_t n_boxes, XhipK9Plan* plan);
+// Sealed boxes, mode 0 opens and 1 seals: epk(32) || tag(16) sit in front of
+// the ciphertext, at src_off - 48 of an open and at dst_off - 48 of a seal
+// (which writes all 48). host_upload is laid out as XhipK9Plan says; K9
+// derives every box's key and nonce on the device, then the K8 kernels run as
+// in xhip_k8_box_run. Every offset is checked before any launch.
+hipError_t xhip_k9_sealbox_run(int mode, uint8_t* host_upload, uint32_t n_boxes, void* work,
+                               uint64_t work_bytes, const uint8_t* src, uint64_t src_bytes,
+                               uint8_t* dst, uint64_t dst_bytes, uint32_t* ok);
+
 }  // extern "C"

@@ -36,6 +36,7 @@
 // bits) take the CPU oracle.
 #include "kernels.h"
 #include "box_stream.h"  // after kernels.h: needs the HIP runtime declared
+#include "fe25519.h"
 #include "mask_quant.h"
 #include "model_codec.h"
 #include "u192.h"
@@ -3106,41 +3107,36 @@ hipError_t xhip_k8_plan(const uint64_t* lens, uint32_t n_boxes, uint32_t* first_
     return hipSuccess;
 }
 
-hipError_t xhip_k8_box_run(int mode, XhipBox* host_boxes, uint32_t n_boxes, void* work,
-                           uint64_t work_bytes, const uint8_t* src, uint64_t src_bytes,
-                           uint8_t* dst, uint64_t dst_bytes, uint32_t* ok) {
-    if (mode != BS_OPEN && mode != BS_SEAL && mode != BS_MAC) return hipErrorInvalidValue;
-    if (n_boxes == 0) return hipSuccess;
-    if (!host_boxes || !work || !src || !dst || !ok || reinterpret_cast<uintptr_t>(work) % 16 ||
-        reinterpret_cast<uintptr_t>(src) % 16 || reinterpret_cast<uintptr_t>(dst) % 16)
-        return hipErrorInvalidValue;
-    // every byte the kernels touch, checked here: whole 16-byte slots of the
-    // message in src (and dst), the tag in front of it (at dst_off for a MAC)
+// The host half of a K8 launch: plans the tiles, fills first_tile and checks
+// every byte the kernels touch: whole 16-byte slots of the message in src (and
+// dst) and `head` bytes in front of the ciphertext (the tag; a sealed box's
+// ephemeral key too), at dst_off itself for a MAC.
+static hipError_t k8_prepare(int mode, XhipBox* host_boxes, uint32_t n_boxes, uint64_t head,
+                             uint64_t src_bytes, uint64_t dst_bytes, XhipK8Plan* plan) {
     std::vector<uint64_t> lens(n_boxes);
     for (uint32_t i = 0; i < n_boxes; ++i) lens[i] = host_boxes[i].len;
     std::vector<uint32_t> first(n_boxes + 1);
-    XhipK8Plan plan;
-    hipError_t e = xhip_k8_plan(lens.data(), n_boxes, first.data(), &plan);
+    hipError_t e = xhip_k8_plan(lens.data(), n_boxes, first.data(), plan);
     if (e != hipSuccess) return e;
-    if (work_bytes < plan.work_bytes) return hipErrorInvalidValue;
     for (uint32_t i = 0; i < n_boxes; ++i) {
         XhipBox& x = host_boxes[i];
         x.first_tile = first[i];
         const uint64_t span = k8_round_up(x.len, 16);
-        const uint64_t src_front = mode == BS_OPEN ? 16 : 0, dst_front = mode == BS_SEAL ? 16 : 0;
+        const uint64_t src_front = mode == BS_OPEN ? head : 0, dst_front = mode == BS_SEAL ? head : 0;
         const uint64_t dst_span = mode == BS_MAC ? 16 : span;
         if (x.src_off % 16 || x.dst_off % 16 ||
             x.src_off < src_front || x.src_off > src_bytes || span > src_bytes - x.src_off ||
             x.dst_off < dst_front || x.dst_off > dst_bytes || dst_span > dst_bytes - x.dst_off)
             return hipErrorInvalidValue;
     }
-    uint8_t* base = static_cast<uint8_t*>(work);
-    XhipBox* boxes = reinterpret_cast<XhipBox*>(base);
-    bs_box_keys* rows = reinterpret_cast<bs_box_keys*>(base + plan.rows_off);
-    uint32_t* partials = reinterpret_cast<uint32_t*>(base + plan.partials_off);
-    e = hipMemcpy(boxes, host_boxes, sizeof(XhipBox) * uint64_t(n_boxes), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return e;
-    const dim3 per_box((n_boxes + WAVE - 1) / WAVE), tiles(plan.total_tiles);
+    return hipSuccess;
+}
+
+// The device half: the four launches over descriptors already on the device.
+static hipError_t k8_launch(int mode, XhipBox* boxes, bs_box_keys* rows, uint32_t* partials,
+                            uint32_t n_boxes, uint32_t total_tiles, const uint8_t* src,
+                            uint8_t* dst, uint32_t* ok) {
+    const dim3 per_box((n_boxes + WAVE - 1) / WAVE), tiles(total_tiles);
     auto run = [&](auto m) {
         constexpr int MODE = decltype(m)::value;
         hipLaunchKernelGGL(k8_box_keys<MODE == BS_MAC>, per_box, dim3(WAVE), 0, 0, boxes, rows, n_boxes);
@@ -3155,4 +3151,171 @@ hipError_t xhip_k8_box_run(int mode, XhipBox* host_boxes, uint32_t n_boxes, void
     if (mode == BS_OPEN) return run(std::integral_constant<int, BS_OPEN>{});
     if (mode == BS_SEAL) return run(std::integral_constant<int, BS_SEAL>{});
     return run(std::integral_constant<int, BS_MAC>{});
+}
+
+hipError_t xhip_k8_box_run(int mode, XhipBox* host_boxes, uint32_t n_boxes, void* work,
+                           uint64_t work_bytes, const uint8_t* src, uint64_t src_bytes,
+                           uint8_t* dst, uint64_t dst_bytes, uint32_t* ok) {
+    if (mode != BS_OPEN && mode != BS_SEAL && mode != BS_MAC) return hipErrorInvalidValue;
+    if (n_boxes == 0) return hipSuccess;
+    if (!host_boxes || !work || !src || !dst || !ok || reinterpret_cast<uintptr_t>(work) % 16 ||
+        reinterpret_cast<uintptr_t>(src) % 16 || reinterpret_cast<uintptr_t>(dst) % 16)
+        return hipErrorInvalidValue;
+    XhipK8Plan plan;
+    hipError_t e = k8_prepare(mode, host_boxes, n_boxes, 16, src_bytes, dst_bytes, &plan);
+    if (e != hipSuccess) return e;
+    if (work_bytes < plan.work_bytes) return hipErrorInvalidValue;
+    uint8_t* base = static_cast<uint8_t*>(work);
+    XhipBox* boxes = reinterpret_cast<XhipBox*>(base);
+    e = hipMemcpy(boxes, host_boxes, sizeof(XhipBox) * uint64_t(n_boxes), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return e;
+    return k8_launch(mode, boxes, reinterpret_cast<bs_box_keys*>(base + plan.rows_off),
+                     reinterpret_cast<uint32_t*>(base + plan.partials_off), n_boxes,
+                     plan.total_tiles, src, dst, ok);
+}
+
+// ------------------------- K9: batched X25519, sealed-box keys on the device
+//
+// The per-box half of a sealed box that K8 left on the host: the Montgomery
+// ladder (fe25519.h, where the arithmetic lives), HSalsa20 of its output and
+// the BLAKE2b nonce. k9_x25519 runs one ladder per lane with x1, x2, z2, x3,
+// z3 and the temporaries in registers for all 255 steps; workgroups are one
+// wave, so the waves of a small batch spread over the CUs. k9_box_agree, one
+// lane per box, turns the ladder outputs into the key and nonce of the XhipBox
+// row that k8_box_keys reads next. Each kernel overwrites or zeroes the secret
+// it is the last to read: the ladder its scalar, agree the shared secret.
+
+__device__ __forceinline__ void k9_load8(uint32_t w[8], const void* p) {
+    const u32x4 a = reinterpret_cast<const u32x4*>(p)[0], b = reinterpret_cast<const u32x4*>(p)[1];
+    w[0] = a.x, w[1] = a.y, w[2] = a.z, w[3] = a.w;
+    w[4] = b.x, w[5] = b.y, w[6] = b.z, w[7] = b.w;
+}
+
+__device__ __forceinline__ void k9_store8(void* p, const uint32_t w[8]) {
+    reinterpret_cast<u32x4*>(p)[0] = u32x4{w[0], w[1], w[2], w[3]};
+    reinterpret_cast<u32x4*>(p)[1] = u32x4{w[4], w[5], w[6], w[7]};
+}
+
+// GATHER: the point of ladder i is the ephemeral key in front of box i
+template <bool GATHER>
+__global__ void __launch_bounds__(WAVE) k9_x25519(XhipLadder* __restrict__ rows, uint32_t n,
+                                                  const XhipBox* __restrict__ boxes,
+                                                  const uint8_t* __restrict__ src) {
+    const uint32_t i = blockIdx.x * WAVE + threadIdx.x;
+    if (i >= n) return;
+    uint32_t scalar[8], point[8], out[8];
+    k9_load8(scalar, rows[i].scalar);
+    if (GATHER)
+        k9_load8(point, src + boxes[i].src_off - 48);
+    else
+        k9_load8(point, rows[i].point);
+    fe_x25519(out, scalar, point);
+    k9_store8(rows[i].scalar, out);
+}
+
+// One lane per box: key = HSalsa20(shared, 0), nonce = BLAKE2b-24(epk || pk).
+template <int MODE>
+__global__ void __launch_bounds__(WAVE) k9_box_agree(XhipBox* __restrict__ boxes,
+                                                     XhipLadder* __restrict__ rows, uint32_t n,
+                                                     const uint8_t* __restrict__ src,
+                                                     uint8_t* __restrict__ dst) {
+    const uint32_t b = blockIdx.x * WAVE + threadIdx.x;
+    if (b >= n) return;
+    uint32_t shared[8], key[8], epk[8], pk[8], nonce[6];
+    k9_load8(shared, rows[b].scalar);
+    k9_load8(pk, rows[b].point);
+    const uint32_t zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    bs_hsalsa(key, shared, zero);
+    if (MODE == BS_OPEN) {
+        k9_load8(epk, src + boxes[b].src_off - 48);
+    } else {
+        k9_load8(epk, rows[n + b].scalar);  // X25519(esk, 9)
+        k9_store8(dst + boxes[b].dst_off - 48, epk);
+        k9_store8(rows[n + b].scalar, zero);
+    }
+    fe_seal_nonce(nonce, epk, pk);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) boxes[b].key[i] = key[i];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) boxes[b].nonce[i] = nonce[i];
+    k9_store8(rows[b].scalar, zero);
+}
+
+hipError_t xhip_k9_x25519_run(XhipLadder* host_rows, uint32_t n, void* work,
+                              uint64_t work_bytes) {
+    if (n == 0) return hipSuccess;
+    if (!host_rows || !work || reinterpret_cast<uintptr_t>(work) % 16 ||
+        work_bytes < sizeof(XhipLadder) * uint64_t(n))
+        return hipErrorInvalidValue;
+    XhipLadder* rows = static_cast<XhipLadder*>(work);
+    hipError_t e = hipMemcpy(rows, host_rows, sizeof(XhipLadder) * uint64_t(n), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k9_x25519<false>, dim3((n + WAVE - 1) / WAVE), dim3(WAVE), 0, 0, rows, n,
+                       static_cast<const XhipBox*>(nullptr), static_cast<const uint8_t*>(nullptr));
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return hipMemcpy(host_rows, rows, sizeof(XhipLadder) * uint64_t(n), hipMemcpyDeviceToHost);
+}
+
+hipError_t xhip_k9_plan(int mode, const uint64_t* lens, uint32_t n_boxes, XhipK9Plan* plan) {
+    *plan = XhipK9Plan{};
+    if (mode != BS_OPEN && mode != BS_SEAL) return hipErrorInvalidValue;
+    if (n_boxes > 0x3fffffffu) return hipErrorInvalidValue;  // two ladders a box in u32
+    std::vector<uint32_t> first(size_t(n_boxes) + 1);
+    XhipK8Plan k8;
+    hipError_t e = xhip_k8_plan(lens, n_boxes, first.data(), &k8);
+    if (e != hipSuccess) return e;
+    plan->ladders = mode == BS_SEAL ? 2 * n_boxes : n_boxes;
+    plan->total_tiles = k8.total_tiles;
+    plan->ladders_off = k8_round_up(sizeof(XhipBox) * uint64_t(n_boxes), 64);
+    plan->upload_bytes = plan->ladders_off + sizeof(XhipLadder) * uint64_t(plan->ladders);
+    plan->rows_off = plan->upload_bytes;
+    plan->partials_off =
+        k8_round_up(plan->rows_off + sizeof(bs_box_keys) * uint64_t(n_boxes), 64);
+    plan->work_bytes = plan->partials_off + 32 * uint64_t(k8.total_tiles);
+    return hipSuccess;
+}
+
+hipError_t xhip_k9_sealbox_run(int mode, uint8_t* host_upload, uint32_t n_boxes, void* work,
+                               uint64_t work_bytes, const uint8_t* src, uint64_t src_bytes,
+                               uint8_t* dst, uint64_t dst_bytes, uint32_t* ok) {
+    if (mode != BS_OPEN && mode != BS_SEAL) return hipErrorInvalidValue;
+    if (n_boxes == 0) return hipSuccess;
+    if (!host_upload || !work || !src || !dst || !ok || reinterpret_cast<uintptr_t>(work) % 16 ||
+        reinterpret_cast<uintptr_t>(src) % 16 || reinterpret_cast<uintptr_t>(dst) % 16)
+        return hipErrorInvalidValue;
+    XhipBox* host_boxes = reinterpret_cast<XhipBox*>(host_upload);
+    std::vector<uint64_t> lens(n_boxes);
+    for (uint32_t i = 0; i < n_boxes; ++i) lens[i] = host_boxes[i].len;
+    XhipK9Plan plan;
+    hipError_t e = xhip_k9_plan(mode, lens.data(), n_boxes, &plan);
+    if (e != hipSuccess) return e;
+    if (work_bytes < plan.work_bytes) return hipErrorInvalidValue;
+    // 48 bytes in front of every ciphertext: what agree reads or writes there
+    // is inside src / dst as the tag is
+    XhipK8Plan k8;
+    e = k8_prepare(mode, host_boxes, n_boxes, 48, src_bytes, dst_bytes, &k8);
+    if (e != hipSuccess) return e;
+    uint8_t* base = static_cast<uint8_t*>(work);
+    XhipBox* boxes = reinterpret_cast<XhipBox*>(base);
+    XhipLadder* ladders = reinterpret_cast<XhipLadder*>(base + plan.ladders_off);
+    e = hipMemcpy(base, host_upload, plan.upload_bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return e;
+    const dim3 per_ladder((plan.ladders + WAVE - 1) / WAVE), per_box((n_boxes + WAVE - 1) / WAVE);
+    if (mode == BS_OPEN) {
+        hipLaunchKernelGGL(k9_x25519<true>, per_ladder, dim3(WAVE), 0, 0, ladders, plan.ladders,
+                           boxes, src);
+        hipLaunchKernelGGL(k9_box_agree<BS_OPEN>, per_box, dim3(WAVE), 0, 0, boxes, ladders,
+                           n_boxes, src, dst);
+    } else {
+        hipLaunchKernelGGL(k9_x25519<false>, per_ladder, dim3(WAVE), 0, 0, ladders, plan.ladders,
+                           boxes, src);
+        hipLaunchKernelGGL(k9_box_agree<BS_SEAL>, per_box, dim3(WAVE), 0, 0, boxes, ladders,
+                           n_boxes, src, dst);
+    }
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return k8_launch(mode, boxes, reinterpret_cast<bs_box_keys*>(base + plan.rows_off),
+                     reinterpret_cast<uint32_t*>(base + plan.partials_off), n_boxes,
+                     plan.total_tiles, src, dst, ok);
 }

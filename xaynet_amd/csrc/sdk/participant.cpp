@@ -212,11 +212,24 @@ void Participant::step_update() {
     p.update_signature = update_signature_;
     p.masked = std::move(masked);
     p.local_seed_dict.reserve(sums->size());
+    std::optional<std::vector<Seed80>> boxes;
+    if (seal_seed_hook_) {
+        std::vector<Key32> ephm_pks;
+        ephm_pks.reserve(sums->size());
+        for (const auto& [sum_pk, ephm_pk] : *sums) ephm_pks.push_back(ephm_pk);
+        boxes = seal_seed_hook_(seed, ephm_pks);
+        if (boxes && boxes->size() != sums->size()) boxes.reset();
+    }
+    size_t at = 0;
     for (const auto& [sum_pk, ephm_pk] : *sums) {
-        Bytes enc = crypto::sealbox_seal(seed, 32, ephm_pk.data());
         msg::LocalSeedEntry e;
         e.pk = sum_pk;
-        std::memcpy(e.seed.data(), enc.data(), 80);
+        if (boxes) {
+            std::memcpy(e.seed.data(), (*boxes)[at++].data(), 80);
+        } else {
+            Bytes enc = crypto::sealbox_seal(seed, 32, ephm_pk.data());
+            std::memcpy(e.seed.data(), enc.data(), 80);
+        }
         p.local_seed_dict.push_back(std::move(e));
     }
 
@@ -234,7 +247,24 @@ void Participant::step_sum2() {
     // encrypted to our ephemeral keypair
     std::vector<std::array<uint8_t, 32>> plain_seeds;
     plain_seeds.reserve(seeds->size());
+    std::optional<std::vector<std::optional<Key32>>> opened;
+    if (open_seeds_hook_) {
+        std::vector<Seed80> enc;
+        enc.reserve(seeds->size());
+        for (const auto& [update_pk, enc_seed] : *seeds) {
+            Seed80 b;
+            std::memcpy(b.data(), enc_seed.data(), 80);
+            enc.push_back(b);
+        }
+        opened = open_seeds_hook_(enc, ephm_pk_, ephm_sk_);
+        if (opened && opened->size() != seeds->size()) opened.reset();
+    }
+    size_t at = 0;
     for (const auto& [update_pk, enc_seed] : *seeds) {
+        if (opened) {
+            if (const auto& s = (*opened)[at++]) plain_seeds.push_back(*s);
+            continue;
+        }
         Bytes seed;
         if (!crypto::sealbox_open(seed, enc_seed.data(), 80, ephm_pk_, ephm_sk_)) continue;
         if (seed.size() != 32) continue;

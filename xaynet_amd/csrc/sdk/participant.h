@@ -130,7 +130,20 @@ class Participant {
     using Sum2Hook = std::function<std::optional<Bytes>(
         const std::vector<std::array<uint8_t, 32>>& seeds, size_t length,
         const std::array<int, 8>& cfg)>;
+    // Seed-dict hooks: the batched sealed-box path (X25519 and the boxes on
+    // the GPU) instead of one crypto::sealbox_open / sealbox_seal a seed.
+    // open: one entry per encrypted seed, in order, nullopt where the tag
+    // fails. seal: one 80-byte box per key. nullopt from either, or an answer
+    // of the wrong shape, falls back to the CPU loop.
+    using Seed80 = std::array<uint8_t, 80>;
+    using OpenSeedsHook = std::function<std::optional<std::vector<std::optional<Key32>>>(
+        const std::vector<Seed80>& enc_seeds, const uint8_t ephm_pk[32],
+        const uint8_t ephm_sk[32])>;
+    using SealSeedHook = std::function<std::optional<std::vector<Seed80>>(
+        const uint8_t seed[32], const std::vector<Key32>& ephm_pks)>;
     void set_mask_model_hook(MaskModelHook h) { mask_hook_ = std::move(h); }
+    void set_open_seeds_hook(OpenSeedsHook h) { open_seeds_hook_ = std::move(h); }
+    void set_seal_seed_hook(SealSeedHook h) { seal_seed_hook_ = std::move(h); }
     void set_sum2_hook(Sum2Hook h) { sum2_hook_ = std::move(h); }
 
     // introspection for tests
@@ -197,6 +210,8 @@ class Participant {
 
     MaskModelHook mask_hook_;
     Sum2Hook sum2_hook_;
+    OpenSeedsHook open_seeds_hook_;
+    SealSeedHook seal_seed_hook_;
 };
 
 }  // namespace xaynet::sdk

@@ -300,6 +300,65 @@ void bind_sdk(py::module_& m) {
                          return Bytes(s.begin(), s.end());
                      });
              })
+        .def("set_open_seeds_hook",
+             [](Participant& p, py::function fn) {
+                 // fn(enc_seeds: list[bytes(80)], ephm_pk, ephm_sk)
+                 // -> list[bytes(32) | None] | None. Anything of another shape
+                 // counts as None: the CPU loop opens the seeds.
+                 p.set_open_seeds_hook(
+                     [fn](const std::vector<Participant::Seed80>& enc, const uint8_t pk[32],
+                          const uint8_t sk[32])
+                         -> std::optional<std::vector<std::optional<Key32>>> {
+                         py::gil_scoped_acquire gil;
+                         py::list ls;
+                         for (const auto& b : enc)
+                             ls.append(py::bytes(reinterpret_cast<const char*>(b.data()), 80));
+                         py::object r = fn(ls, py::bytes(reinterpret_cast<const char*>(pk), 32),
+                                           py::bytes(reinterpret_cast<const char*>(sk), 32));
+                         if (r.is_none() || !py::isinstance<py::list>(r)) return std::nullopt;
+                         py::list out = r;
+                         if (out.size() != enc.size()) return std::nullopt;
+                         std::vector<std::optional<Key32>> seeds(enc.size());
+                         for (size_t i = 0; i < enc.size(); ++i) {
+                             py::object o = out[i];
+                             if (o.is_none()) continue;
+                             if (!py::isinstance<py::bytes>(o)) return std::nullopt;
+                             std::string v = py::cast<py::bytes>(o);
+                             if (v.size() != 32) return std::nullopt;
+                             Key32 k;
+                             std::memcpy(k.data(), v.data(), 32);
+                             seeds[i] = k;
+                         }
+                         return seeds;
+                     });
+             })
+        .def("set_seal_seed_hook",
+             [](Participant& p, py::function fn) {
+                 // fn(seed: bytes(32), ephm_pks: list[bytes(32)])
+                 // -> list[bytes(80)] | None
+                 p.set_seal_seed_hook(
+                     [fn](const uint8_t seed[32], const std::vector<Key32>& pks)
+                         -> std::optional<std::vector<Participant::Seed80>> {
+                         py::gil_scoped_acquire gil;
+                         py::list ls;
+                         for (const auto& k : pks)
+                             ls.append(py::bytes(reinterpret_cast<const char*>(k.data()), 32));
+                         py::object r =
+                             fn(py::bytes(reinterpret_cast<const char*>(seed), 32), ls);
+                         if (r.is_none() || !py::isinstance<py::list>(r)) return std::nullopt;
+                         py::list out = r;
+                         if (out.size() != pks.size()) return std::nullopt;
+                         std::vector<Participant::Seed80> boxes(pks.size());
+                         for (size_t i = 0; i < pks.size(); ++i) {
+                             py::object o = out[i];
+                             if (!py::isinstance<py::bytes>(o)) return std::nullopt;
+                             std::string v = py::cast<py::bytes>(o);
+                             if (v.size() != 80) return std::nullopt;
+                             std::memcpy(boxes[i].data(), v.data(), 80);
+                         }
+                         return boxes;
+                     });
+             })
         .def("save_reference", [](const Participant& p) { return pyb(p.save_reference()); })
         .def_static(
             "restore_reference",

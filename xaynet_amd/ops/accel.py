@@ -7,6 +7,8 @@ Usage:
     # or: xaynet_sdk.Participant(url, gpu=True) / spawn_participant(gpu=True)
     # ParticipantAccel(exact=True) / spawn_participant(gpu=True, gpu_exact=True):
     # the masked update equals the CPU masker's byte for byte
+    # ParticipantAccel(gpu_seeds=True) / spawn_participant(gpu=True, gpu_seeds=True):
+    # the seed dicts are sealed and opened in batches on the GPU (K9 + K8)
 
 The hooks receive the round's mask config + model length from the SDK and
 lazily build (and cache) one engine per (config, length). They fall back to
@@ -31,8 +33,10 @@ _NP_DTYPES = {0: np.float32, 1: np.float64, 2: np.int32, 3: np.int64}
 
 class ParticipantAccel:
     def __init__(self, device: str = "cuda:0", scalar_num: int = 1, scalar_den: int = 1,
-                 exact: bool = False):
-        """exact=False masks with the constructor's scalar through the
+                 exact: bool = False, gpu_seeds: bool = False):
+        """gpu_seeds=True also takes the seed-dict hooks: the 80-byte sealed
+        seeds of the update and sum2 tasks go through GpuBox.seal_seed /
+        open_seeds, X25519 included. exact=False masks with the constructor's scalar through the
         double-precision K5w kernel. exact=True masks with the scalar the hook
         hands over (the participant's own) in exact mode: the update is the
         CPU masker's, byte for byte."""
@@ -43,6 +47,8 @@ class ParticipantAccel:
         self.scalar_num = scalar_num
         self.scalar_den = scalar_den
         self.exact = exact
+        self.gpu_seeds = gpu_seeds
+        self._box = None  # the seed hooks' GpuBox, built on first use
         # one accelerator may be shared by many participants (threads): the
         # engines + scratch are serialized under a lock
         self._mu = threading.Lock()
@@ -99,6 +105,31 @@ class ParticipantAccel:
                 LOG.exception("GPU sum2 hook failed; falling back to CPU")
                 return None
 
+    def _seed_box(self):
+        if self._box is None:
+            from .box import GpuBox
+
+            self._box = GpuBox(device=self.device)
+        return self._box
+
+    def open_seeds(self, enc_seeds, ephm_pk: bytes, ephm_sk: bytes):
+        """The sum2 task's seed dict: 32-byte seeds, None where a tag fails."""
+        with self._mu:
+            try:
+                return self._seed_box().open_seeds(enc_seeds, ephm_pk, ephm_sk)
+            except Exception:  # noqa: BLE001 — CPU fallback
+                LOG.exception("GPU open_seeds hook failed; falling back to CPU")
+                return None
+
+    def seal_seed(self, seed: bytes, ephm_pks):
+        """The update task's seed dict: one 80-byte box per sum participant."""
+        with self._mu:
+            try:
+                return self._seed_box().seal_seed(seed, ephm_pks)
+            except Exception:  # noqa: BLE001 — CPU fallback
+                LOG.exception("GPU seal_seed hook failed; falling back to CPU")
+                return None
+
     # Bodies shorter than this stay on the CPU decoder in decode_model. 0: the
     # kernel path is 4.7x ahead at 1M f32 weights and 5.5x at 25M, and at 10k
     # it is 0.06 ms behind, less than the upload the CPU result would still
@@ -150,17 +181,20 @@ class ParticipantAccel:
     def attach(self, participant) -> None:
         participant.set_mask_model_hook(self.mask_model)
         participant.set_sum2_hook(self.aggregate_masks)
+        if self.gpu_seeds:
+            participant.set_open_seeds_hook(self.open_seeds)
+            participant.set_seal_seed_hook(self.seal_seed)
 
 
-_SHARED = {}  # exact flag -> the process-wide ParticipantAccel
+_SHARED = {}  # (exact, gpu_seeds) -> the process-wide ParticipantAccel
 _SHARED_MU = threading.Lock()
 
 
-def shared_accel(exact: bool = False) -> ParticipantAccel:
+def shared_accel(exact: bool = False, gpu_seeds: bool = False) -> ParticipantAccel:
     """The process-wide accelerator of the SDK's gpu=True participants, one per
-    flag value (its engines are cached per round config)."""
-    exact = bool(exact)
+    pair of flag values (its engines are cached per round config)."""
+    key = (bool(exact), bool(gpu_seeds))
     with _SHARED_MU:
-        if exact not in _SHARED:
-            _SHARED[exact] = ParticipantAccel(exact=exact)
-        return _SHARED[exact]
+        if key not in _SHARED:
+            _SHARED[key] = ParticipantAccel(exact=key[0], gpu_seeds=key[1])
+        return _SHARED[key]

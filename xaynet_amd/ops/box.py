@@ -6,8 +6,11 @@ A batch lives in one packed device buffer. Every box gets `_HEAD` bytes of
 head room and its message starts on a 64-byte boundary, so the kernels' 16-byte
 accesses are aligned, the tag (and a sealed box's ephemeral key) sit right in
 front of the ciphertext, and an opened payload is a 16-byte-aligned view that a
-later kernel can read in place. X25519 and the sealed-box nonce (blake2b) stay
-on the host; only the bulk pass over the bytes runs on the device.
+later kernel can read in place. By default X25519 and the sealed-box nonce
+(blake2b) stay on the host and only the bulk pass over the bytes runs on the
+device; `device_keys=True` moves them to the device as well (K9: one Montgomery
+ladder per lane, then HSalsa20 and the nonce per box), and `open_seeds` /
+`seal_seed` are the seed-dict forms of that path.
 
 The kernels decrypt and authenticate in one pass, so plaintext of a forged
 box does exist in the output buffer for a moment: a last kernel zeroes it, and
@@ -26,6 +29,7 @@ from .engine import _hip, _require_gpu
 _OPEN, _SEAL, _MAC = 0, 1, 2
 _HEAD = 64  # bytes in front of every message: room for epk(32) || tag(16)
 _crypto = _core.crypto
+_BASE_POINT = bytes([9]) + bytes(31)
 
 
 def _nbytes(item):
@@ -65,6 +69,7 @@ class GpuBox:
         self._pin = None  # pinned staging buffer, grown on demand, wiped after a seal
         self.opened_buffer = self.opened_offsets = None
         self._work = None
+        self._up = None  # pinned descriptors and scalars of a sealed-box run, wiped by each
 
     # ---------------- packing ----------------
 
@@ -123,6 +128,57 @@ class GpuBox:
                 self.kernel_ms = t0.elapsed_time(t1)
         return ok
 
+    def _run_sealed(self, mode, lens, sk, pks, src, src_offs, dst, dst_offs):
+        """K9 then K8: as _run, the keys and nonces derived on the device.
+        sk: the recipient's secret key (open); a seal's ephemeral secret keys
+        are drawn here. pks: 32 bytes, or 32 a box (seal)."""
+        n = len(lens)
+        with torch.cuda.device(self.device):
+            work_bytes, up_bytes, ladders_off = _hip._sealbox_plan(mode, lens)
+            if self._work is None or self._work.numel() < work_bytes:
+                self._work = self._new(work_bytes)
+            if self._up is None or self._up.numel() < up_bytes:
+                self._up = torch.empty(up_bytes, dtype=torch.uint8).pin_memory()
+            ok = torch.empty(n, dtype=torch.int32, device=self.device)
+            if mode == _SEAL:
+                # the host's randombytes, straight into the scalars of the
+                # ladder rows: the pinned upload buffer holds the only host
+                # copy, and the binding zeroes that buffer after the upload
+                rows = self._up.numpy()[ladders_off:ladders_off + 64 * n].reshape(n, 64)
+                _crypto.randombytes_into(rows[:, :32])
+            if self.time_kernels:
+                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0.record()
+            _hip._sealbox_run(mode, self._up.data_ptr(), self._up.numel(), sk, pks, lens,
+                              src_offs, dst_offs, src.data_ptr(), src.numel(), dst.data_ptr(),
+                              dst.numel(), self._work.data_ptr(), self._work.numel(),
+                              ok.data_ptr())
+            if self.time_kernels:
+                t1.record()
+                t1.synchronize()
+                self.kernel_ms = t0.elapsed_time(t1)
+        return ok
+
+    # ---------------- X25519 ----------------
+
+    def x25519_batch(self, scalars, points=None):
+        """X25519(scalar, point) of every pair on the device, one ladder per
+        lane (K9); `points=None` is the base point. Returns 32-byte values. No
+        low-order-point rejection: such a point gives 32 zero bytes, as
+        `_core.crypto.x25519` does."""
+        scalars = [bytes(s) for s in scalars]
+        points = [_BASE_POINT] * len(scalars) if points is None else [bytes(p) for p in points]
+        if len(points) != len(scalars) or any(len(v) != 32 for v in scalars + points):
+            raise ValueError("one 32-byte scalar and one 32-byte point a ladder")
+        if not scalars:
+            return []
+        with torch.cuda.device(self.device):
+            if self._work is None or self._work.numel() < 64 * len(scalars):
+                self._work = self._new(64 * len(scalars))
+            out = _hip._x25519_batch(b"".join(scalars), b"".join(points), self._work.data_ptr(),
+                                     self._work.numel())
+        return [out[32 * i:32 * i + 32] for i in range(len(scalars))]
+
     # ---------------- secretbox ----------------
 
     def secretbox_open_batch(self, boxes, keys, nonces):
@@ -142,6 +198,10 @@ class GpuBox:
         dst = self._new(total)
         good = self._run(_OPEN, lens, [keys[i] for i in live], [nonces[i] for i in live], src,
                          offs, dst, offs).bool()
+        return self._opened(out, ok, live, offs, lens, dst, good)
+
+    def _opened(self, out, ok, live, offs, lens, dst, good):
+        """What an open hands back: views of the boxes whose tag matched."""
         ok[torch.tensor(live, device=self.device)] = good
         self.opened_buffer = dst
         for i, off, m, g in zip(live, offs, lens, good.tolist()):
@@ -174,10 +234,14 @@ class GpuBox:
 
     # ---------------- sealed boxes ----------------
 
-    def sealbox_open_batch(self, sealed, pk, sk):
+    def sealbox_open_batch(self, sealed, pk, sk, device_keys=False):
         """Open epk || tag || cipher sealed boxes addressed to (pk, sk): as
-        secretbox_open_batch, with the key agreement per box on the host."""
+        secretbox_open_batch, with the key agreement per box on the host, or,
+        with `device_keys`, on the device: no host ladder and no read back of
+        a device input's ephemeral key."""
         pk, sk = bytes(pk), bytes(sk)
+        if device_keys:
+            return self._sealbox_open_device(sealed, pk, sk)
         boxes, keys, nonces = [], [], []
         for s in sealed:
             if isinstance(s, torch.Tensor):
@@ -194,11 +258,34 @@ class GpuBox:
             nonces.append(_crypto.blake2b(epk + pk, 24))
         return self.secretbox_open_batch(boxes, keys, nonces)
 
-    def sealbox_seal_batch(self, messages, pk):
+    def _sealbox_open_device(self, sealed, pk, sk):
+        if len(pk) != 32 or len(sk) != 32:
+            raise ValueError("keys are 32 bytes")
+        n = len(sealed)
+        live = [i for i in range(n) if _nbytes(sealed[i]) >= 48]
+        ok = torch.zeros(n, dtype=torch.bool, device=self.device)
+        out = [None] * n
+        self.opened_buffer, self.opened_offsets = None, [None] * n
+        if not live:
+            return out, ok
+        lens = [_nbytes(sealed[i]) - 48 for i in live]
+        offs, total = _layout(lens)
+        src = self._pack([sealed[i] for i in live], offs, 48, total)
+        dst = self._new(total)
+        good = self._run_sealed(_OPEN, lens, sk, pk, src, offs, dst, offs).bool()
+        return self._opened(out, ok, live, offs, lens, dst, good)
+
+    def sealbox_seal_batch(self, messages, pk, device_keys=False):
         """Seal to pk with a fresh ephemeral key per message; returns uint8
-        device tensors epk || tag || cipher."""
+        device tensors epk || tag || cipher. With `device_keys`, pk is one key
+        or one key per message, and the ephemeral secret keys (32 bytes a box
+        from the host's randombytes) go up once with the descriptors: both
+        ladders of a box, its key and its nonce are computed on the device."""
         if not len(messages):
             return []
+        if device_keys:
+            dst, offs, lens = self._sealbox_seal_device(messages, pk)
+            return [dst[off - 48:off + m] for off, m in zip(offs, lens)]
         pk = bytes(pk)
         heads, keys, nonces = [], [], []
         for _ in messages:
@@ -207,6 +294,61 @@ class GpuBox:
             keys.append(_crypto.box_beforenm(pk, esk))
             nonces.append(_crypto.blake2b(epk + pk, 24))
         return self._seal(messages, keys, nonces, heads)
+
+    def _sealbox_seal_device(self, messages, pk):
+        one = isinstance(pk, (bytes, bytearray, memoryview))
+        pks = bytes(pk) if one else b"".join(bytes(k) for k in pk)
+        if len(pks) != (32 if one else 32 * len(messages)) or \
+                (not one and any(len(bytes(k)) != 32 for k in pk)):
+            raise ValueError("one 32-byte key, or one a message")
+        lens = [_nbytes(m) for m in messages]
+        offs, total = _layout(lens)
+        src = self._pack(messages, offs, 0, total, wipe=True)
+        dst = self._new(total)
+        self._run_sealed(_SEAL, lens, b"", pks, src, offs, dst, offs)
+        return dst, offs, lens
+
+    # ---------------- seed dicts ----------------
+
+    # Batches below this stay on `_core.crypto`, one box at a time. A call
+    # costs about 1 ms whatever the batch (one ladder is 0.69 ms deep), the CPU
+    # 41 us a seed opened and 81 us sealed: at 16 seeds the CPU opens faster
+    # (0.65 against 1.12 ms), at 64 the device does (1.09 against 2.59 ms open,
+    # 0.94 against 5.14 ms seal), the smallest measured size where it wins both
+    # ways (scripts/box_bench.py --device-keys --seed-sweep,
+    # profiles/r19_x25519_gpu.md).
+    SEEDS_MIN_BATCH = 64
+
+    def open_seeds(self, enc_seeds, pk, sk):
+        """Open the 80-byte sealed seeds of a sum2 seed dict: 32-byte seeds as
+        host bytes, None where the tag fails (or the entry is no 80 bytes)."""
+        enc_seeds = [bytes(e) for e in enc_seeds]
+        pk, sk = bytes(pk), bytes(sk)
+        if len(enc_seeds) < self.SEEDS_MIN_BATCH:
+            return [_crypto.sealbox_open(e, pk, sk) if len(e) == 80 else None for e in enc_seeds]
+        live = [i for i, e in enumerate(enc_seeds) if len(e) == 80]
+        out = [None] * len(enc_seeds)
+        if not live:
+            return out
+        _, ok = self.sealbox_open_batch([enc_seeds[i] for i in live], pk, sk, device_keys=True)
+        host = self.opened_buffer.cpu().numpy()
+        for i, off, good in zip(live, self.opened_offsets, ok.tolist()):
+            if good:
+                out[i] = host[off:off + 32].tobytes()
+        self.opened_buffer.zero_()  # plain seeds: the host copy is the one handed on
+        return out
+
+    def seal_seed(self, seed, pks):
+        """Seal one 32-byte seed to every key of `pks`: 80-byte boxes as host
+        bytes, in order."""
+        seed, pks = bytes(seed), [bytes(k) for k in pks]
+        if len(seed) != 32:
+            raise ValueError("a seed is 32 bytes")
+        if len(pks) < self.SEEDS_MIN_BATCH:
+            return [_crypto.sealbox_seal(seed, k) for k in pks]
+        dst, offs, _ = self._sealbox_seal_device([seed] * len(pks), pks)
+        host = dst.cpu().numpy()
+        return [host[off - 48:off + 32].tobytes() for off in offs]
 
     # ---------------- the MAC alone ----------------
 

@@ -26,6 +26,7 @@ def spawn_participant(
     scalar: float = 1.0,
     gpu: bool = False,
     gpu_exact: bool = False,
+    gpu_seeds: bool = False,
 ):
     """Spawn an `InternalParticipant` thread and return its handle. If `state`
     is given, the participant is restored from it. `scalar` weights this
@@ -33,9 +34,11 @@ def spawn_participant(
     `gpu=True` runs the update-masking and sum2 mask-aggregation hot loops
     on a visible MI355X (falls back to CPU per call on any error); with
     `gpu_exact=True` the masked update is the CPU masker's byte for byte and
-    uses this participant's `scalar`."""
+    uses this participant's `scalar`; with `gpu_seeds=True` the seed dicts of
+    the update and sum2 tasks are sealed and opened in batches on the GPU."""
     internal_participant = InternalParticipant(
-        coordinator_url, participant, args, kwargs, state, scalar, gpu=gpu, gpu_exact=gpu_exact
+        coordinator_url, participant, args, kwargs, state, scalar, gpu=gpu, gpu_exact=gpu_exact,
+        gpu_seeds=gpu_seeds
     )
     internal_participant.start()
     return internal_participant

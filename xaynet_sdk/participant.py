@@ -73,11 +73,12 @@ class ParticipantABC(ABC):
 
 class InternalParticipant(threading.Thread):
     def __init__(self, coordinator_url, participant, p_args, p_kwargs, state, scalar,
-                 gpu=False, gpu_exact=False):
+                 gpu=False, gpu_exact=False, gpu_seeds=False):
         # gpu=True: the shared process-wide accelerator (one per flag value)
         # takes the masking and sum2 hooks and serves global_model_tensor()
         self._xaynet_participant = xaynet_sdk.Participant(coordinator_url, scalar, state,
-                                                          gpu=gpu, gpu_exact=gpu_exact)
+                                                          gpu=gpu, gpu_exact=gpu_exact,
+                                                          gpu_seeds=gpu_seeds)
 
         # the user participant is constructed on the thread (run()) so the ML
         # model lives on the participant thread (reference participant.py:129-149)

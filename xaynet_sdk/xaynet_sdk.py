@@ -99,11 +99,12 @@ class Participant:
     """API-compatible wrapper of the native participant state machine."""
 
     def __init__(self, coordinator_url: str, scalar: float = 1.0, state=None, *,
-                 gpu: bool = False, gpu_exact: bool = False, client=None):
+                 gpu: bool = False, gpu_exact: bool = False, gpu_seeds: bool = False,
+                 client=None):
         """gpu=True attaches the process-wide participant accelerator (update
         masking and the sum2 mask sum on the GPU; gpu_exact as for
-        spawn_participant) and makes global_model_tensor() decode on the
-        device. client, an XaynetClient such as _core.sdk.InProcessClient,
+        spawn_participant; gpu_seeds also moves the seed dicts' sealed boxes
+        there) and makes global_model_tensor() decode on the device. client, an XaynetClient such as _core.sdk.InProcessClient,
         replaces the HTTP client of coordinator_url, which is then unused."""
         if client is None:
             host, port = _parse_url(coordinator_url)
@@ -114,7 +115,7 @@ class Participant:
         if gpu:
             from xaynet_amd.ops.accel import shared_accel
 
-            self._accel = shared_accel(gpu_exact)
+            self._accel = shared_accel(gpu_exact, gpu_seeds)
             self._accel.attach(self._inner)
 
     def _init_native(self, scalar, state):
