@@ -23,8 +23,16 @@ GpuBox.open_seeds / seal_seed (host bytes in and out) against the CPU loop over
 batch sizes, which is what GpuBox.SEEDS_MIN_BATCH is read from, and
 x25519_batch against `_core.crypto.x25519`.
 
+--verify measures K10: GpuBox.verify_batch over 64 .. 65536 signatures (powers
+of four) of 38-byte and 4 KiB messages against `_core.crypto.verify_detached`
+on one core (timed up to 4096 signatures), and GpuBox.open_messages against
+`sealbox_open_batch(device_keys=True)` followed by a CPU verify loop over the
+plaintexts copied back. Rounds alternate after a warm-up that compares every
+result with the CPU's.
+
 Usage (GPU box): python scripts/box_bench.py [--reps 5] [--shapes 1x175000000,64x8388608]
                  python scripts/box_bench.py --device-keys [--seed-sweep]
+                 python scripts/box_bench.py --verify
 """
 import argparse
 import json
@@ -124,13 +132,73 @@ def device_keys_bench(args):
                           **{k + "_ms": spread(v) for k, v in t.items() if v}}), flush=True)
 
 
+def verify_bench(args):
+    box = GpuBox("cuda:0", time_kernels=True)
+    rng = np.random.default_rng(20)
+    spk, ssk = cr.sign_keypair_from_seed(b"\x43" * 32)
+    for size in (38, 4096):
+        msgs = [rng.bytes(size) for _ in range(65536)]
+        sigs = [cr.sign_detached(m, ssk) for m in msgs]
+        for j in range(0, 65536, 5):  # every fifth signature is wrong
+            sigs[j] = sigs[j][:40] + bytes([sigs[j][40] ^ 1]) + sigs[j][41:]
+        for n in (64, 256, 1024, 4096, 16384, 65536):
+            g, m = sigs[:n], msgs[:n]
+            got = box.verify_batch(g, m, spk)
+            assert got == [j % 5 != 0 for j in range(n)]
+            if n <= 4096:
+                assert got == [cr.verify_detached(a, b, spk) for a, b in zip(g, m)]
+            t = {"kernel": [], "call": [], "cpu": []}
+            for _ in range(args.reps):
+                t["call"] += timed(lambda: box.verify_batch(g, m, spk), 1)
+                t["kernel"].append(box.kernel_ms)
+                if n <= 4096:
+                    t["cpu"] += timed(lambda: [cr.verify_detached(a, b, spk)
+                                               for a, b in zip(g, m)], 1)
+            print(json.dumps({"op": "verify_batch", "signatures": n, "bytes_per_message": size,
+                              "reps": args.reps,
+                              **{k + "_ms": spread(v) for k, v in t.items() if v}}), flush=True)
+    # update messages of 4 KiB: three signatures each
+    pk, sk = cr.box_seed_keypair(b"\x42" * 32)
+    seed = b"\x5e" * 32
+    tasks = cr.sign_detached(seed + b"sum", ssk) + cr.sign_detached(seed + b"update", ssk)
+    for n in (64, 1024, 4096):
+        sealed = []
+        for _ in range(n):
+            body = spk + pk + (4096).to_bytes(4, "big") + bytes([2, 0, 0, 0]) + tasks + \
+                rng.bytes(4096 - 264)
+            sealed.append(bytes(cr.sealbox_seal(cr.sign_detached(body, ssk) + body, pk)))
+
+        def host_path():
+            box.sealbox_open_batch(sealed, pk, sk, device_keys=True)
+            host = box.opened_buffer.cpu().numpy()
+            out = []
+            for off in box.opened_offsets:
+                p = host[off:off + 4096].tobytes()
+                out.append(cr.verify_detached(p[:64], p[64:], p[64:96]) +
+                           2 * cr.verify_detached(p[136:200], seed + b"sum", p[64:96]) +
+                           4 * cr.verify_detached(p[200:264], seed + b"update", p[64:96]))
+            return out
+
+        assert box.open_messages(sealed, pk, sk, round_seed=seed)[1] == host_path() == [7] * n
+        t = {"open_messages": [], "open_then_cpu_verify": []}
+        for _ in range(args.reps):
+            t["open_messages"] += timed(lambda: box.open_messages(sealed, pk, sk, seed), 1)
+            t["open_then_cpu_verify"] += timed(host_path, 1)
+        print(json.dumps({"op": "open_messages", "messages": n, "bytes_per_message": 4096,
+                          "reps": args.reps, **{k + "_ms": spread(v) for k, v in t.items()}}),
+              flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--shapes", default=None)
     ap.add_argument("--device-keys", action="store_true")
     ap.add_argument("--seed-sweep", action="store_true")
+    ap.add_argument("--verify", action="store_true")
     args = ap.parse_args()
+    if args.verify:
+        return verify_bench(args)
     if args.device_keys:
         return device_keys_bench(args)
     args.shapes = args.shapes or "1x175000000,64x8388608,4096x4096"

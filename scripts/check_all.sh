@@ -39,6 +39,10 @@ build/unmask_round_sanitize
 # the K9 ladder, field arithmetic and sealed-box nonce (fe25519.h) over the edge points
 g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
     -Ixaynet_amd/csrc scripts/x25519_sanitize.cpp -o build/x25519_sanitize
+# the K10 signature check (ed25519.h) over the RFC 8032 vectors and the edge keys and scalars
+g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all \
+    -Ixaynet_amd/csrc scripts/ed25519_sanitize.cpp -o build/ed25519_sanitize
+build/ed25519_sanitize
 build/x25519_sanitize
 bash scripts/sanitize.sh
 bash scripts/tsan.sh

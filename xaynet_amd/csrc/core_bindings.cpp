@@ -17,6 +17,7 @@
 #include "crypto/poly1305.h"
 #include "crypto/sha2.h"
 #include "gpu/box_stream.h"
+#include "gpu/ed25519.h"
 #include "gpu/fe25519.h"
 
 namespace py = pybind11;
@@ -248,6 +249,35 @@ PYBIND11_MODULE(_core, m) {
         fe_x25519(shared, sw, ew);
         bs_hsalsa(key, shared, zero);
         return to_pybytes(reinterpret_cast<const uint8_t*>(key), 32);
+    });
+    // The K10 arithmetic (gpu/ed25519.h) on the host: the whole signature
+    // check as the device runs it, and two of its stages on their own.
+    c.def("ed25519_verify_host", [](py::bytes sig, py::bytes msg, py::bytes pk) {
+        Bytes g = from_pybytes(sig), m_ = from_pybytes(msg), p = from_pybytes(pk);
+        if (g.size() != 64 || p.size() != 32)
+            throw py::value_error("a signature is 64 bytes, a key 32");
+        return ed25519_verify_host(g.data(), m_.data(), m_.size(), p.data());
+    });
+    c.def("sc_reduce512_host", [](py::bytes bytes64) {
+        Bytes b = from_pybytes(bytes64);
+        if (b.size() != 64) throw py::value_error("64 bytes");
+        uint32_t in[16], out[8];
+        std::memcpy(in, b.data(), 64);
+        sc_reduce512(out, in);
+        return to_pybytes(reinterpret_cast<const uint8_t*>(out), 32);
+    });
+    // (x, y) as canonical 32-byte values, or None where the key is no point
+    c.def("ed25519_decompress_host", [](py::bytes pk) -> py::object {
+        Bytes p = from_pybytes(pk);
+        if (p.size() != 32) throw py::value_error("a key is 32 bytes");
+        uint32_t w[8], x[8], y[8];
+        std::memcpy(w, p.data(), 32);
+        ge_ext a;
+        if (!ge_decompress(a, w)) return py::none();
+        fe_tobytes(x, a.X);
+        fe_tobytes(y, a.Y);
+        return py::make_tuple(to_pybytes(reinterpret_cast<const uint8_t*>(x), 32),
+                              to_pybytes(reinterpret_cast<const uint8_t*>(y), 32));
     });
     c.def("randombytes", [](size_t n) {
         Bytes out(n);

@@ -801,6 +801,56 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("src"), py::arg("src_bytes"), py::arg("dst"), py::arg("dst_bytes"),
         py::arg("work"), py::arg("work_bytes"), py::arg("ok"));
 
+    // private (ops/box.py): the device workspace _verify_run takes for n signatures
+    m.def(
+        "_verify_plan",
+        [](uint32_t n) {
+            XhipK10Plan plan;
+            xhip_k10_plan(n, &plan);
+            return plan.work_bytes;
+        },
+        py::arg("n"));
+
+    // private (ops/box.py): K10 over one batch. Signature i is the 64 bytes at
+    // sig_offs[i] and the key at pk_offs[i] of the device buffer `data`, its
+    // message the msg_lens[i] bytes at msg_offs[i] of `data`, or of `extra`
+    // where msg_bufs[i] is 1. ok: one device u32 a signature, 1 where it
+    // verifies. Every offset is checked before any launch (kernels.h).
+    m.def(
+        "_verify_run",
+        [](const std::vector<uint64_t>& sig_offs, const std::vector<uint64_t>& pk_offs,
+           const std::vector<uint64_t>& msg_offs, const std::vector<uint64_t>& msg_lens,
+           const std::vector<uint32_t>& msg_bufs, uintptr_t data, uint64_t data_bytes,
+           uintptr_t extra, uint64_t extra_bytes, uintptr_t work, uint64_t work_bytes,
+           uintptr_t ok) {
+            const size_t n = sig_offs.size();
+            if (pk_offs.size() != n || msg_offs.size() != n || msg_lens.size() != n ||
+                msg_bufs.size() != n || n > 0xffffffffu)
+                throw py::value_error("_verify_run: one signature, key, message offset, "
+                                      "length and buffer a signature");
+            std::vector<XhipSig> sigs(n);
+            for (size_t i = 0; i < n; ++i) {
+                if (msg_lens[i] > 0xffffffffu)
+                    throw py::value_error("_verify_run: a message is below 2^32 bytes");
+                sigs[i] = XhipSig{sig_offs[i], pk_offs[i], msg_offs[i], uint32_t(msg_lens[i]),
+                                  msg_bufs[i], uint32_t(i), 0};
+            }
+            hipError_t e;
+            {
+                py::gil_scoped_release release;
+                e = xhip_k10_verify_run(sigs.data(), uint32_t(n), reinterpret_cast<void*>(work),
+                                        work_bytes, u8p(data), data_bytes, u8p(extra),
+                                        extra_bytes, reinterpret_cast<uint32_t*>(ok));
+            }
+            if (e == hipErrorInvalidValue)
+                throw py::value_error("_verify_run: an offset, a length or the workspace does "
+                                      "not fit");
+            check(e, "k10_verify_run");
+        },
+        py::arg("sig_offs"), py::arg("pk_offs"), py::arg("msg_offs"), py::arg("msg_lens"),
+        py::arg("msg_bufs"), py::arg("data"), py::arg("data_bytes"), py::arg("extra"),
+        py::arg("extra_bytes"), py::arg("work"), py::arg("work_bytes"), py::arg("ok"));
+
     // [n_planes][len] digit planes minus the mask -> model weights.
     // dtype follows mask::DataType: 0=F32 1=F64 2=I32 3=I64
     // Bmax configs, and integer outputs of the other bounds, pass `offset` =

@@ -376,4 +376,31 @@ hipError_t xhip_k9_sealbox_run(int mode, uint8_t* host_upload, uint32_t n_boxes,
                                uint64_t work_bytes, const uint8_t* src, uint64_t src_bytes,
                                uint8_t* dst, uint64_t dst_bytes, uint32_t* ok);
 
+// ---- K10: batched Ed25519 verification ----
+//
+// One signature of a batch: byte offsets of what is read in place. The 64
+// signature bytes and the 32 key bytes lie in `data` on 4-byte boundaries; the
+// message lies in `data` (msg_buf 0) or in `extra` (msg_buf 1) on a 16-byte
+// boundary, and its last 16-byte slot is read whole, so it has to be inside
+// the buffer. ok[index] receives the verdict; `blocks` (the SHA-512 blocks of
+// R || A || M) is the launcher's, which orders the batch by it.
+struct XhipSig {
+    uint64_t sig_off, pk_off, msg_off;
+    uint32_t msg_len, msg_buf, index, blocks;
+};  // 40 bytes
+// The workspace of a batch: the descriptors at 0, 32 bytes of k a signature
+// at rows_off.
+struct XhipK10Plan {
+    uint64_t rows_off, work_bytes;
+};
+hipError_t xhip_k10_plan(uint32_t n, XhipK10Plan* plan);
+// ok[index] = 1 where the signature verifies by the rules of ed25519.h (those
+// of crypto::ed25519_verify), else 0. host_sigs is host memory, reordered here;
+// every index is below n and every offset is checked against data_bytes /
+// extra_bytes before any launch (hipErrorInvalidValue). extra may be null
+// where no descriptor names it. Lengths run from 0 to 2^32 - 1.
+hipError_t xhip_k10_verify_run(XhipSig* host_sigs, uint32_t n, void* work, uint64_t work_bytes,
+                               const uint8_t* data, uint64_t data_bytes, const uint8_t* extra,
+                               uint64_t extra_bytes, uint32_t* ok);
+
 }  // extern "C"

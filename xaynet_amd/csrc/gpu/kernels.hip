@@ -36,6 +36,7 @@
 // bits) take the CPU oracle.
 #include "kernels.h"
 #include "box_stream.h"  // after kernels.h: needs the HIP runtime declared
+#include "ed25519.h"
 #include "fe25519.h"
 #include "mask_quant.h"
 #include "model_codec.h"
@@ -43,6 +44,7 @@
 #include "unmask_round.h"
 
 #include <algorithm>
+#include <mutex>
 
 #define WAVE 64
 
@@ -3318,4 +3320,235 @@ hipError_t xhip_k9_sealbox_run(int mode, uint8_t* host_upload, uint32_t n_boxes,
     return k8_launch(mode, boxes, reinterpret_cast<bs_box_keys*>(base + plan.rows_off),
                      reinterpret_cast<uint32_t*>(base + plan.partials_off), n_boxes,
                      plan.total_tiles, src, dst, ok);
+}
+
+// ------------------------------ K10: batched Ed25519 verification
+//
+// Two launches over descriptors (XhipSig) of byte offsets into the caller's
+// device buffers; nothing is copied. k10_hram computes k = SHA-512(R || A || M)
+// mod L per signature into the work row that k10_verify, which checks
+// encode(s B - k A) == R, reads next. The arithmetic and the acceptance rules
+// live in ed25519.h. One signature per lane, one wave per workgroup, so that
+// the waves of a small batch spread over the CUs as K9's do.
+//
+// k10_hram: the lanes' messages lie at 64 unrelated offsets, so a lane reading
+// its own 128-byte block would touch 64 scattered lines per load. For every
+// block that lies wholly inside its lane's message the wave stages instead:
+// eight threads cover one lane's block with 16-byte loads (512 chunks, eight
+// rounds), and chunk q of lane l goes to LDS slot q * 64 + ((l + 2 q) & 63).
+// A lane then reads its chunk q from 64 consecutive 16-byte slots across the
+// wave, and the sixteen threads of a write pass (two lanes' blocks, q = 0..7)
+// fall in sixteen distinct slots mod 16 (l + 2 q over an even and an odd l).
+// The first block (R, A, the message head) and the blocks that hold the tail
+// and the padding are assembled per lane with guarded 16-byte loads and
+// sha512_block_words' masks. The launcher orders descriptors by block count,
+// so that a wave's lanes run out of blocks together.
+//
+// k10_verify: the table of 1..8 times -A is per lane and lives in LDS, lane
+// minor: word w of entry e of lane l at (e * 40 + w) * 64 + l, so a lane stays
+// in its own bank whatever its digit (80 KiB a wave). B's table, 8 x 30 words,
+// is one copy: entries start 30 words apart, so eight distinct entries begin in
+// distinct banks. The running point and both scalars' digits stay in registers.
+// Signed radix 16 was built: 64 windows of four doublings and two additions.
+
+__device__ uint32_t k10_base_table[240];  // 1 B .. 8 B (ed_base_table), set once per device
+
+__device__ __forceinline__ void k10_load_words(uint32_t* w, const uint8_t* p, int n) {
+    const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
+#pragma unroll
+    for (int i = 0; i < n; ++i) w[i] = q[i];
+}
+
+__device__ __forceinline__ void k10_chunk(uint32_t* m, const uint8_t* msg, uint64_t at,
+                                          uint32_t len) {
+    u32x4 v{0, 0, 0, 0};
+    if (at < len) v = *reinterpret_cast<const u32x4*>(msg + at);  // whole slots: checked by the host
+    m[0] = v.x, m[1] = v.y, m[2] = v.z, m[3] = v.w;
+}
+
+__global__ void __launch_bounds__(WAVE) k10_hram(const XhipSig* __restrict__ sigs, uint32_t n,
+                                                 const uint8_t* __restrict__ data,
+                                                 const uint8_t* __restrict__ extra,
+                                                 uint32_t* __restrict__ krows) {
+    __shared__ u32x4 stage[WAVE * 8];
+    const uint32_t lane = threadIdx.x, i = blockIdx.x * WAVE + lane;
+    const bool live = i < n;
+    XhipSig s{};
+    if (live) s = sigs[i];
+    const uint8_t* msg = (s.msg_buf ? extra : data) + s.msg_off;
+    const uint64_t total = uint64_t(s.msg_len) + 64;
+    const uint32_t blocks = live ? uint32_t(sha512_blocks(total)) : 0;
+    uint32_t most = blocks;
+#pragma unroll
+    for (int d = WAVE / 2; d > 0; d >>= 1) most = max(most, uint32_t(__shfl_xor(int(most), d)));
+    uint32_t head[16] = {};
+    if (live) {
+        k10_load_words(head, data + s.sig_off, 8);
+        k10_load_words(head + 8, data + s.pk_off, 8);
+    }
+    const uint64_t at0 = reinterpret_cast<uint64_t>(msg);
+    uint64_t st[8], w[16];
+    sha512_init(st);
+#pragma unroll 1
+    for (uint32_t b = 0; b < most; ++b) {
+        const bool mine = b < blocks;
+        const bool whole = b >= 1 && 128 * (uint64_t(b) + 1) <= total && mine;
+        uint32_t m[32];
+        if (__any(whole)) {
+#pragma unroll
+            for (int t = 0; t < 8; ++t) {
+                const uint32_t c = t * WAVE + lane, l = c >> 3, q = c & 7;
+                const uint64_t from = uint64_t(uint32_t(__shfl(int(uint32_t(at0)), l))) |
+                                      uint64_t(uint32_t(__shfl(int(uint32_t(at0 >> 32)), l))) << 32;
+                if (__shfl(int(whole), l))
+                    stage[q * WAVE + ((l + 2 * q) & (WAVE - 1))] = *reinterpret_cast<const u32x4*>(
+                        from + 128 * uint64_t(b) - 64 + 16 * q);
+            }
+            __syncthreads();
+            if (whole) {
+#pragma unroll
+                for (int q = 0; q < 8; ++q) {
+                    const u32x4 v = stage[q * WAVE + ((lane + 2 * q) & (WAVE - 1))];
+                    m[4 * q] = v.x, m[4 * q + 1] = v.y, m[4 * q + 2] = v.z, m[4 * q + 3] = v.w;
+                }
+            }
+            __syncthreads();
+        }
+        if (mine && !whole) {
+            if (b == 0) {
+#pragma unroll
+                for (int j = 0; j < 16; ++j) m[j] = head[j];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) k10_chunk(m + 16 + 4 * q, msg, 16 * q, s.msg_len);
+            } else {
+#pragma unroll
+                for (int q = 0; q < 8; ++q)
+                    k10_chunk(m + 4 * q, msg, 128 * uint64_t(b) - 64 + 16 * q, s.msg_len);
+            }
+        }
+        if (mine) {
+            sha512_block_words(w, m, b, total);
+            sha512_compress(st, w);
+        }
+    }
+    if (!live) return;
+    uint32_t digest[16], k[8];
+    sha512_digest_words(digest, st);
+    sc_reduce512(k, digest);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) krows[8 * uint64_t(i) + j] = k[j];
+}
+
+#define K10_ENTRY 40  // words of a cached entry
+
+__global__ void __launch_bounds__(WAVE) k10_verify(const XhipSig* __restrict__ sigs, uint32_t n,
+                                                   const uint8_t* __restrict__ data,
+                                                   const uint32_t* __restrict__ krows,
+                                                   uint32_t* __restrict__ ok) {
+    __shared__ uint32_t ta[8 * K10_ENTRY * WAVE];
+    __shared__ uint32_t tb[240];
+    const uint32_t lane = threadIdx.x, i = blockIdx.x * WAVE + lane;
+    for (uint32_t w = lane; w < 240; w += WAVE) tb[w] = k10_base_table[w];
+    __syncthreads();
+    if (i >= n) return;  // no barrier below: a lane reads back only what it wrote
+    const XhipSig s = sigs[i];
+    uint32_t sig[16], pk[8], k[8];
+    k10_load_words(sig, data + s.sig_off, 16);
+    k10_load_words(pk, data + s.pk_off, 8);
+    k10_load_words(k, reinterpret_cast<const uint8_t*>(krows + 8 * uint64_t(i)), 8);
+    uint32_t* mine = ta + lane;
+    auto base = [&](uint32_t e) {
+        ge_pre q;
+#pragma unroll
+        for (int w = 0; w < 10; ++w) {
+            q.ypx.v[w] = tb[30 * e + w];
+            q.ymx.v[w] = tb[30 * e + 10 + w];
+            q.xy2d.v[w] = tb[30 * e + 20 + w];
+        }
+        return q;
+    };
+    auto put = [&](int e, const ge_cached& c) {
+#pragma unroll
+        for (int w = 0; w < 10; ++w) {
+            mine[(K10_ENTRY * e + w) * WAVE] = c.ypx.v[w];
+            mine[(K10_ENTRY * e + 10 + w) * WAVE] = c.ymx.v[w];
+            mine[(K10_ENTRY * e + 20 + w) * WAVE] = c.z.v[w];
+            mine[(K10_ENTRY * e + 30 + w) * WAVE] = c.t2d.v[w];
+        }
+    };
+    auto cached = [&](uint32_t e) {
+        ge_cached q;
+#pragma unroll
+        for (int w = 0; w < 10; ++w) {
+            q.ypx.v[w] = mine[(K10_ENTRY * e + w) * WAVE];
+            q.ymx.v[w] = mine[(K10_ENTRY * e + 10 + w) * WAVE];
+            q.z.v[w] = mine[(K10_ENTRY * e + 20 + w) * WAVE];
+            q.t2d.v[w] = mine[(K10_ENTRY * e + 30 + w) * WAVE];
+        }
+        return q;
+    };
+    ok[s.index] = ed_check(sig, pk, k, base, put, cached);
+}
+
+hipError_t xhip_k10_plan(uint32_t n, XhipK10Plan* plan) {
+    *plan = XhipK10Plan{};
+    plan->rows_off = k8_round_up(sizeof(XhipSig) * uint64_t(n), 64);
+    plan->work_bytes = plan->rows_off + 32 * uint64_t(n);
+    return hipSuccess;
+}
+
+// B's table on the current device, uploaded the first time the device is seen
+static hipError_t k10_base_ready() {
+    static std::mutex mu;
+    static uint64_t seen = 0;
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    std::lock_guard<std::mutex> lock(mu);
+    if (dev < 64 && (seen >> dev & 1)) return hipSuccess;
+    e = hipMemcpyToSymbol(HIP_SYMBOL(k10_base_table), ed_base_table(), 240 * sizeof(uint32_t));
+    if (e == hipSuccess && dev < 64) seen |= uint64_t(1) << dev;
+    return e;
+}
+
+hipError_t xhip_k10_verify_run(XhipSig* host_sigs, uint32_t n, void* work, uint64_t work_bytes,
+                               const uint8_t* data, uint64_t data_bytes, const uint8_t* extra,
+                               uint64_t extra_bytes, uint32_t* ok) {
+    if (n == 0) return hipSuccess;
+    if (!host_sigs || !work || !data || !ok || reinterpret_cast<uintptr_t>(work) % 16 ||
+        reinterpret_cast<uintptr_t>(data) % 16 || reinterpret_cast<uintptr_t>(extra) % 16)
+        return hipErrorInvalidValue;
+    XhipK10Plan plan;
+    xhip_k10_plan(n, &plan);
+    if (work_bytes < plan.work_bytes) return hipErrorInvalidValue;
+    // every byte a kernel reads: 64 of the signature, 32 of the key, whole
+    // 16-byte slots of the message
+    bool mixed = false;
+    for (uint32_t i = 0; i < n; ++i) {
+        XhipSig& s = host_sigs[i];
+        const uint64_t bytes = s.msg_buf == 0 ? data_bytes : extra_bytes;
+        const uint64_t span = k8_round_up(s.msg_len, 16);
+        if (s.sig_off % 4 || s.pk_off % 4 || s.msg_off % 16 || s.msg_buf > 1 ||
+            (s.msg_buf == 1 && !extra) || s.index >= n ||
+            s.sig_off > data_bytes || 64 > data_bytes - s.sig_off ||
+            s.pk_off > data_bytes || 32 > data_bytes - s.pk_off ||
+            s.msg_off > bytes || span > bytes - s.msg_off)
+            return hipErrorInvalidValue;
+        s.blocks = uint32_t(sha512_blocks(uint64_t(s.msg_len) + 64));
+        mixed = mixed || s.blocks != host_sigs[0].blocks;
+    }
+    if (mixed)
+        std::stable_sort(host_sigs, host_sigs + n,
+                         [](const XhipSig& a, const XhipSig& b) { return a.blocks < b.blocks; });
+    hipError_t e = k10_base_ready();
+    if (e != hipSuccess) return e;
+    uint8_t* base = static_cast<uint8_t*>(work);
+    XhipSig* sigs = reinterpret_cast<XhipSig*>(base);
+    uint32_t* krows = reinterpret_cast<uint32_t*>(base + plan.rows_off);
+    e = hipMemcpy(sigs, host_sigs, sizeof(XhipSig) * uint64_t(n), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return e;
+    const dim3 grid((n + WAVE - 1) / WAVE);
+    hipLaunchKernelGGL(k10_hram, grid, dim3(WAVE), 0, 0, sigs, n, data, extra, krows);
+    hipLaunchKernelGGL(k10_verify, grid, dim3(WAVE), 0, 0, sigs, n, data, krows, ok);
+    return hipGetLastError();
 }

@@ -350,6 +350,105 @@ class GpuBox:
         host = dst.cpu().numpy()
         return [host[off - 48:off + 32].tobytes() for off in offs]
 
+    # ---------------- Ed25519 ----------------
+
+    def _verify(self, sig_offs, pk_offs, msg_offs, msg_lens, msg_bufs, data, extra=None):
+        """K10 over descriptors into `data` (and `extra`): one 0 / 1 a signature."""
+        n = len(sig_offs)
+        with torch.cuda.device(self.device):
+            work_bytes = _hip._verify_plan(n)
+            if self._work is None or self._work.numel() < work_bytes:
+                self._work = self._new(work_bytes)
+            ok = torch.empty(n, dtype=torch.int32, device=self.device)
+            if self.time_kernels:
+                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0.record()
+            _hip._verify_run(sig_offs, pk_offs, msg_offs, msg_lens, msg_bufs, data.data_ptr(),
+                             data.numel(), 0 if extra is None else extra.data_ptr(),
+                             0 if extra is None else extra.numel(), self._work.data_ptr(),
+                             self._work.numel(), ok.data_ptr())
+            if self.time_kernels:
+                t1.record()
+                t1.synchronize()
+                self.kernel_ms = t0.elapsed_time(t1)
+        return ok.tolist()
+
+    def verify_batch(self, signatures, messages, pks):
+        """Ed25519: whether signatures[i] is one of messages[i] under pks[i]
+        (or under the one key `pks`), a list of bools. Items are host buffers
+        or device tensors. Always on the device (K10), with the acceptance
+        rules of `_core.crypto.verify_detached`: s >= L and keys that are no
+        point are rejected, keys and R of small order are not."""
+        n = len(signatures)
+        one = isinstance(pks, (bytes, bytearray, memoryview, torch.Tensor))
+        keys = [pks] if one else list(pks)
+        if len(messages) != n or (not one and len(keys) != n) or \
+                any(_nbytes(g) != 64 for g in signatures) or any(_nbytes(k) != 32 for k in keys):
+            raise ValueError("one 64-byte signature and one message each, one 32-byte key or "
+                             "one each")
+        if n == 0:
+            return []
+        # key(s) | signatures | messages, every message on a 64-byte boundary
+        lens = [_nbytes(m) for m in messages]
+        pk_offs = [32 * i for i in range(len(keys))]
+        at = (32 * len(keys) + 63) // 64 * 64
+        sig_offs = [at + 64 * i for i in range(n)]
+        at += 64 * n
+        msg_offs = []
+        for m in lens:
+            msg_offs.append(at)
+            at += (m + 63) // 64 * 64
+        data = self._pack(keys + list(signatures) + list(messages), pk_offs + sig_offs + msg_offs,
+                          0, at + _HEAD)
+        ok = self._verify(sig_offs, pk_offs * n if one else pk_offs, msg_offs, lens, [0] * n, data)
+        return [bool(v) for v in ok]
+
+    def open_messages(self, sealed, pk, sk, round_seed=None):
+        """Open sealed PET messages (K9, K8) and check their signatures (K10)
+        where the plaintexts lie on the device. Returns (messages, flags):
+        messages as `sealbox_open_batch` returns them, and an int a message.
+        Bit 0: the box opened, holds a header (136 bytes) whose length field
+        lies in [136, len], and the header signature over [64, length) verifies
+        under the key at [64, 96). With `round_seed`, for a message of tag 1, 2
+        or 3 that is no multipart chunk and long enough: bit 1, the sum
+        signature at 136 verifies over round_seed || "sum"; bit 2 (tag 2), the
+        update signature at 200 over round_seed || "update". A failed
+        signature zeroes nothing; the eligibility threshold stays on the host."""
+        messages, _ = self.sealbox_open_batch(sealed, pk, sk, device_keys=True)
+        flags = [0] * len(messages)
+        live = [i for i, m in enumerate(messages) if m is not None and m.numel() >= 136]
+        if not live:
+            return messages, flags
+        data = self.opened_buffer
+        offs = [self.opened_offsets[i] for i in live]
+        at = torch.tensor(offs, device=self.device)[:, None] + 128 + \
+            torch.arange(6, device=self.device)
+        heads = data[at.reshape(-1)].reshape(-1, 6).cpu().numpy()
+        extra = None
+        if round_seed is not None:  # the two task strings, uploaded once
+            tasks = [bytes(round_seed) + b"sum", bytes(round_seed) + b"update"]
+            task_offs = [0, (len(tasks[0]) + 63) // 64 * 64]
+            extra = self._pack(tasks, task_offs, 0, task_offs[1] + len(tasks[1]) + _HEAD)
+        jobs = []  # (message, bit, signature, message offset, length, buffer)
+        for i, off, head in zip(live, offs, heads):
+            length = int.from_bytes(bytes(head[:4]), "big")
+            if not 136 <= length <= messages[i].numel():
+                continue
+            jobs.append((i, 1, off, off + 64, length - 64, 0))
+            if extra is None or head[5] & 1 or head[4] not in (1, 2, 3):
+                continue
+            if length >= 200:
+                jobs.append((i, 2, off + 136, task_offs[0], len(tasks[0]), 1))
+            if head[4] == 2 and length >= 264:
+                jobs.append((i, 4, off + 200, task_offs[1], len(tasks[1]), 1))
+        if jobs:
+            pk_offs = [self.opened_offsets[j[0]] + 64 for j in jobs]
+            ok = self._verify([j[2] for j in jobs], pk_offs, [j[3] for j in jobs],
+                              [j[4] for j in jobs], [j[5] for j in jobs], data, extra)
+            for (i, bit, *_), good in zip(jobs, ok):
+                flags[i] |= bit * good
+        return messages, flags
+
     # ---------------- the MAC alone ----------------
 
     def poly1305(self, data, key32) -> bytes:
