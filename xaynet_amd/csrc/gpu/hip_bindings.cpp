@@ -851,6 +851,59 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("msg_bufs"), py::arg("data"), py::arg("data_bytes"), py::arg("extra"),
         py::arg("extra_bytes"), py::arg("work"), py::arg("work_bytes"), py::arg("ok"));
 
+    // private (ops/engine.py): how K11 stages n objects of len elements of bpn
+    // bytes, and the workspace _stage_run takes (kernels.h). All zero where
+    // there is no such launch.
+    m.def(
+        "_stage_plan",
+        [](uint64_t len, int bpn, uint32_t n) {
+            XhipK11Plan p;
+            xhip_k11_plan(len, bpn, n, &p);
+            py::dict d;
+            d["tile_elems"] = p.tile_elems;
+            d["depth"] = p.depth;
+            d["waves"] = p.waves;
+            d["span"] = p.span;
+            d["tile_blocks"] = p.tile_blocks;
+            d["has_tail"] = p.has_tail;
+            d["n_tiles"] = p.n_tiles;
+            d["copy_bytes"] = p.copy_bytes;
+            d["bad_off"] = p.bad_off;
+            d["work_bytes"] = p.work_bytes;
+            return d;
+        },
+        py::arg("len"), py::arg("bpn"), py::arg("n"));
+
+    // private (ops/engine.py): K11 over one batch. Object i is the len * bpn
+    // limb bytes at offs[i] of the device buffer `src`; it goes to row
+    // `row` + i of the pool, and the u32 at bad_off + 4 * i of `work` says
+    // afterwards whether an element was not below `order` (the row is then
+    // zeros). Every offset and row is checked before any launch (kernels.h).
+    m.def(
+        "_stage_run",
+        [](uintptr_t src, uint64_t src_bytes, const std::vector<uint64_t>& offs, uint64_t len,
+           int bpn, const std::string& order, uintptr_t pool, uint64_t pool_bytes,
+           uint64_t stride, uint64_t row, uintptr_t work, uint64_t work_bytes) {
+            if (offs.size() > 0xffffffffu) throw py::value_error("_stage_run: the batch is too large");
+            const Limbs o = parse_limbs(order);
+            XhipK11Order words;
+            for (int j = 0; j < 10; ++j) words.w[j] = uint32_t(o.v.w[j / 2] >> (32 * (j % 2)));
+            hipError_t e;
+            {
+                py::gil_scoped_release release;
+                e = xhip_k11_stage_run(u8p(src), src_bytes, offs.data(), uint32_t(offs.size()), len,
+                                       bpn, words, u8p(pool), pool_bytes, stride, row,
+                                       reinterpret_cast<void*>(work), work_bytes);
+            }
+            if (e == hipErrorInvalidValue)
+                throw py::value_error("_stage_run: the bytes per number, the order, an offset, a "
+                                      "row or the workspace does not fit");
+            check(e, "k11_stage_run");
+        },
+        py::arg("src"), py::arg("src_bytes"), py::arg("offs"), py::arg("len"), py::arg("bpn"),
+        py::arg("order"), py::arg("pool"), py::arg("pool_bytes"), py::arg("stride"),
+        py::arg("row"), py::arg("work"), py::arg("work_bytes"));
+
     // [n_planes][len] digit planes minus the mask -> model weights.
     // dtype follows mask::DataType: 0=F32 1=F64 2=I32 3=I64
     // Bmax configs, and integer outputs of the other bounds, pass `offset` =

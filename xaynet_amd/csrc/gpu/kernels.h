@@ -403,4 +403,41 @@ hipError_t xhip_k10_verify_run(XhipSig* host_sigs, uint32_t n, void* work, uint6
                                const uint8_t* data, uint64_t data_bytes, const uint8_t* extra,
                                uint64_t extra_bytes, uint32_t* ok);
 
+// ---- K11: masked vectors, where they lie, into rows of the K3 pool ----
+//
+// The group order as ten little-endian 32-bit words; it reaches the kernel by
+// value.
+struct XhipK11Order {
+    uint32_t w[10];
+};
+// How a batch of n objects of `len` elements of `bpn` bytes is staged. A wave
+// streams `span` tiles of tile_elems elements (K3's tiles: 64 * T elements,
+// whole 1-KiB pieces) through a ring of `depth` LDS slots, and a block is
+// `waves` waves over waves * span adjacent tiles; tile_blocks of them cover the
+// n_tiles full tiles of an object. The bytes from n_tiles * tile_elems * bpn up
+// to copy_bytes = round_up(len * bpn, 16), where there are any (has_tail), go
+// through one more block, block 0. The workspace holds the n source offsets at
+// 0 and one `bad` word an object at bad_off. All zero for a bpn K3 is not
+// instantiated for, len outside [1, 2^32) or n == 0.
+struct XhipK11Plan {
+    uint32_t tile_elems, depth, waves, span, tile_blocks, has_tail;
+    uint64_t n_tiles, copy_bytes, bad_off, work_bytes;
+};
+void xhip_k11_plan(uint64_t len, int bpn, uint32_t n, XhipK11Plan* plan);
+// Object i is the len * bpn limb bytes at src + offs[i]; it is copied, rounded
+// up to 16 bytes, to pool + (row + i) * stride, and the u32 at bad_off + 4 * i
+// of `work` is 1 afterwards if one of its elements, read as a little-endian
+// integer, is not below `order`, else 0. The row of such an object is zeros
+// over its copy_bytes. offs is host memory. Nothing outside
+// [src + offs[i], src + offs[i] + copy_bytes) is read, nothing outside the
+// n rows' copy_bytes is written. hipErrorInvalidValue, before any launch,
+// for: a bpn without a kernel, len outside [1, 2^32), an order that is zero or
+// does not fit bpn bytes, a src, offset, pool, stride or workspace that is not
+// 16-byte aligned, a stride below copy_bytes, a source range outside
+// src_bytes, a row outside pool_bytes, a workspace below work_bytes.
+hipError_t xhip_k11_stage_run(const uint8_t* src, uint64_t src_bytes, const uint64_t* offs,
+                              uint32_t n, uint64_t len, int bpn, XhipK11Order order,
+                              uint8_t* pool, uint64_t pool_bytes, uint64_t stride, uint64_t row,
+                              void* work, uint64_t work_bytes);
+
 }  // extern "C"

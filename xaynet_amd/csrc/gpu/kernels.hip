@@ -44,7 +44,10 @@
 #include "unmask_round.h"
 
 #include <algorithm>
+#include <cstring>
 #include <mutex>
+#include <type_traits>
+#include <vector>
 
 #define WAVE 64
 
@@ -453,18 +456,22 @@ struct K3Tile {
     static_assert(TILE_BYTES % 1024 == 0, "a tile is whole 1-KiB pieces");
 };
 
-// The digits of the element that starts sh bytes (0..3, known at run time
-// only) into w[0], added to a[].
+// Digit d of the element that starts sh bytes (0..3, known at run time only)
+// into w[0].
+template <int BPN, int NW>
+__device__ __forceinline__ uint32_t k3_digit(const uint32_t (&w)[NW], uint32_t sh, int d) {
+    const int nb = (BPN - 4 * d) >= 4 ? 4 : (BPN - 4 * d);
+    uint32_t val = __builtin_amdgcn_alignbyte(d + 1 < NW ? w[d + 1] : 0u, w[d], sh);
+    if (nb < 4) val &= (1u << (8 * nb)) - 1;
+    return val;
+}
+
+// The digits of that element, added to a[].
 template <int BPN, int NW, int NDIG>
 __device__ __forceinline__ void k3_add_digits(const uint32_t (&w)[NW], uint32_t sh,
                                               uint64_t (&a)[NDIG]) {
 #pragma unroll
-    for (int d = 0; d < NDIG; ++d) {
-        const int nb = (BPN - 4 * d) >= 4 ? 4 : (BPN - 4 * d);
-        uint32_t val = __builtin_amdgcn_alignbyte(d + 1 < NW ? w[d + 1] : 0u, w[d], sh);
-        if (nb < 4) val &= (1u << (8 * nb)) - 1;
-        a[d] += uint64_t(val);
-    }
+    for (int d = 0; d < NDIG; ++d) a[d] += uint64_t(k3_digit<BPN>(w, sh, d));
 }
 
 // The remainder block: elements [rem_start, len), fewer than one tile. Thread
@@ -3550,5 +3557,262 @@ hipError_t xhip_k10_verify_run(XhipSig* host_sigs, uint32_t n, void* work, uint6
     const dim3 grid((n + WAVE - 1) / WAVE);
     hipLaunchKernelGGL(k10_hram, grid, dim3(WAVE), 0, 0, sigs, n, data, extra, krows);
     hipLaunchKernelGGL(k10_verify, grid, dim3(WAVE), 0, 0, sigs, n, data, krows, ok);
+    return hipGetLastError();
+}
+
+// ------------------------- K11: opened update messages into the K3 pool
+//
+// After K8..K10 an update message lies opened and verified in device memory;
+// K3 wants its masked vector as a row of the update pool. k11_stage copies the
+// limb bytes of every object of a batch to its row and, in the same pass,
+// decides whether an element is not below the group order: the element-wise
+// half of MaskObject::is_valid. Every object has the same length, so the grid
+// is (blocks of tiles, objects). The tiles are K3's (K3Tile, k3_issue_tile,
+// k3_digit): a wave brings a tile into a slot of its private LDS ring with
+// LDS-DMA loads, D - 1 tiles ahead, writes it out with one coalesced 16-byte
+// store a lane and piece, and reads lane l's elements l + 64k back out of the
+// slot to compare them. Wave w of a block takes tiles w, w + WAVES, ... of the
+// block's WAVES * span adjacent tiles, so a block streams one contiguous range.
+// Only the issuing wave touches its slots: counted waits, no barriers.
+
+// 1 where v >= order, both as NDIG little-endian digits, else 0: whether
+// v - order leaves no borrow. One subtract-with-borrow a digit, the borrow in
+// the carry flag; a comparison from the top digit down keeps two lane masks a
+// digit alive in scalar registers instead, and spilled them. The order's words
+// are the same for every lane.
+template <int NDIG>
+__device__ __forceinline__ uint32_t k11_not_below(const uint32_t (&v)[NDIG],
+                                                  const XhipK11Order& o) {
+    uint64_t t = 0;
+#pragma unroll
+    for (int d = 0; d < NDIG; ++d) t = uint64_t(v[d]) - o.w[d] - (t >> 63);
+    return 1u - uint32_t(t >> 63);
+}
+
+// The ring depth and the waves of a block per bytes-per-number: three slots
+// where a tile is at most 8 KiB, else two, and as many waves, up to four, as
+// keep the rings of two blocks inside a CU's 160 KiB of LDS.
+constexpr int k11_depth(int bpn) { return 64 * k3_tile_t(bpn) * bpn <= 8192 ? 3 : 2; }
+constexpr int k11_waves(int bpn) {
+    const int w = 80 * 1024 / (k11_depth(bpn) * (64 * k3_tile_t(bpn) * bpn + 16));
+    return w > 4 ? 4 : w < 1 ? 1 : w;
+}
+#define K11_SPAN 8  // tiles a wave streams
+
+template <int BPN, int T, int D, int WAVES>
+__global__ __launch_bounds__(WAVES * 64) void k11_stage(
+    const uint8_t* __restrict__ src, const uint64_t* __restrict__ offs,
+    uint8_t* __restrict__ rows, uint64_t stride, uint64_t len, uint32_t n_tiles, uint32_t span,
+    XhipK11Order order, uint32_t* __restrict__ bad) {
+    using Tile = K3Tile<BPN, T>;
+    constexpr int NDIG = Tile::NDIG, NW = Tile::NW, TILE_BYTES = Tile::TILE_BYTES,
+                  PIECES = Tile::PIECES, SLOT_WORDS = Tile::SLOT_WORDS;
+    static_assert(D == 2 || D == 3, "the first D - 1 waits are written out");
+    __shared__ __attribute__((aligned(16))) uint32_t ring[WAVES * D * SLOT_WORDS];
+
+    const uint32_t obj = blockIdx.y;
+    const uint8_t* const in = src + offs[obj];
+    uint8_t* const out = rows + uint64_t(obj) * stride;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint64_t tiled = uint64_t(n_tiles) * TILE_BYTES;
+    const uint64_t copy_bytes = (len * BPN + 15) & ~uint64_t(15);
+    const bool has_tail = tiled < copy_bytes;  // then block 0 is the tail block
+
+    uint32_t over = 0;
+    // the element that starts sh bytes into r[0], in LDS
+    // (forced inline: at sixteen call sites of ten digits the compiler would
+    // rather call it, with its arrays in scratch)
+    auto check = [&](const uint32_t* r, uint32_t sh) __attribute__((always_inline)) {
+        uint32_t w[NW], v[NDIG];
+#pragma unroll
+        for (int j = 0; j < NW; ++j) w[j] = r[j];
+#pragma unroll
+        for (int d = 0; d < NDIG; ++d) v[d] = k3_digit<BPN>(w, sh, d);
+        over |= k11_not_below(v, order);
+    };
+
+    if (has_tail && blockIdx.x == 0) {
+        // The bytes past the last full tile, fewer than TILE_BYTES and whole
+        // 16-byte vectors: plain loads, each stored to the row and to slot 0,
+        // where the elements below len are then read as in a tile. The source
+        // has no padding behind it, so no element is read from global memory
+        // word by word: a slot's four spare words take the overhang.
+        const uint32_t vecs = uint32_t(copy_bytes - tiled) / 16;
+        for (uint32_t i = threadIdx.x; i < vecs; i += WAVES * 64) {
+            const u32x4 x = *reinterpret_cast<const u32x4*>(in + tiled + 16 * uint64_t(i));
+            *reinterpret_cast<u32x4*>(out + tiled + 16 * uint64_t(i)) = x;
+            *reinterpret_cast<u32x4*>(ring + 4 * i) = x;
+        }
+        __syncthreads();
+        const uint32_t rem = uint32_t(len - uint64_t(n_tiles) * (64 * T));
+        for (uint32_t e = threadIdx.x; e < rem; e += WAVES * 64)
+            check(ring + ((e * BPN) >> 2), (e * BPN) & 3);
+    } else {
+        const uint32_t first = (blockIdx.x - uint32_t(has_tail)) * (WAVES * span) + wave;
+        if (first < n_tiles) {  // wave-uniform; there is no barrier below
+            const uint32_t cnt = min(span, (n_tiles - first + WAVES - 1) / WAVES);
+            uint32_t* const wring = ring + wave * (D * SLOT_WORDS);
+            // this lane's 16 bytes of the first piece of tile `first`; the
+            // wave's tile k lies k * WAVES tiles further on
+            const uint64_t at = uint64_t(first) * TILE_BYTES + lane * 16;
+            const uint32_t rword = (lane * BPN) >> 2, rsh = (lane * BPN) & 3;
+
+            auto issue = [&](uint32_t k, uint32_t slot) {
+                k3_issue_tile<BPN, T, 0>(in + at + uint64_t(k) * (WAVES * TILE_BYTES),
+                                         wring + slot * SLOT_WORDS);
+            };
+            auto handle = [&](uint32_t k, uint32_t slot) __attribute__((always_inline)) {
+                const uint32_t* s = wring + slot * SLOT_WORDS;
+                uint8_t* o = out + at + uint64_t(k) * (WAVES * TILE_BYTES);
+#pragma unroll
+                for (int p = 0; p < PIECES; ++p) {
+                    // at most eight pieces in registers at a time: the 37 and
+                    // 39 of the widest tiles at once would spill
+                    if (p % 8 == 0 && p) asm volatile("" ::: "memory");
+                    *reinterpret_cast<u32x4*>(o + p * 1024) =
+                        *reinterpret_cast<const u32x4*>(s + p * 256 + lane * 4);
+                }
+#pragma unroll
+                for (int j = 0; j < T; ++j) check(s + rword + j * 16 * BPN, rsh);
+            };
+            auto next = [](uint32_t slot) { return slot + 1 == D ? 0u : slot + 1; };
+
+            uint32_t wslot = 0, rslot = 0, k = 0;
+            // One tile of the steady state. Stores count in vmcnt like loads
+            // and retire in issue order, and a tile is PIECES of each, so the
+            // wait names how many instructions were issued behind tile k's
+            // loads (at most 63: a smaller count only waits for more).
+            auto step = [&](auto behind) {
+                constexpr int BEHIND = decltype(behind)::value < 63 ? decltype(behind)::value : 63;
+                // the slot about to be filled was read one tile ago
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                issue(k + (D - 1), wslot);
+                wslot = next(wslot);
+                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(BEHIND) : "memory");
+                handle(k, rslot);
+                rslot = next(rslot);
+                ++k;
+            };
+            for (; k < cnt && k < D - 1; ++k) {  // prologue: tiles 0..D-2
+                issue(k, wslot);
+                wslot = next(wslot);
+            }
+            k = 0;
+            // behind tile k's loads: the loads of D - 1 tiles and the stores
+            // of min(k, D - 1)
+            if (k + (D - 1) < cnt) step(std::integral_constant<int, (D - 1) * PIECES>{});
+            if (D == 3 && k + (D - 1) < cnt) step(std::integral_constant<int, D * PIECES>{});
+            while (k + (D - 1) < cnt) step(std::integral_constant<int, 2 * (D - 1) * PIECES>{});
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // drain: the last D-1 tiles
+            for (; k < cnt; ++k) {
+                handle(k, rslot);
+                rslot = next(rslot);
+            }
+        }
+    }
+    // one ballot a wave, and one atomic only where an element was out of range
+    if (__ballot(over != 0) != 0 && lane == 0) atomicOr(bad + obj, 1u);
+}
+
+// Zeroes the copy_bytes of every row whose object had an element out of range,
+// 16 KiB a block; the blocks of good rows return at once.
+__global__ void __launch_bounds__(256) k11_wipe(uint8_t* __restrict__ rows, uint64_t stride,
+                                                uint64_t copy_bytes,
+                                                const uint32_t* __restrict__ bad) {
+    if (!bad[blockIdx.y]) return;
+    u32x4* out = reinterpret_cast<u32x4*>(rows + uint64_t(blockIdx.y) * stride);
+    for (uint32_t p = 0; p < 4; ++p) {
+        const uint64_t i = (uint64_t(blockIdx.x) * 4 + p) * 256 + threadIdx.x;
+        if (i < copy_bytes / 16) out[i] = u32x4{0, 0, 0, 0};
+    }
+}
+
+#define K11_BPNS(X)                                                                             \
+    X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16)       \
+    X(18) X(37) X(38) X(39) X(40)
+
+using K11Kernel = void (*)(const uint8_t*, const uint64_t*, uint8_t*, uint64_t, uint64_t,
+                           uint32_t, uint32_t, XhipK11Order, uint32_t*);
+struct K11Shape {
+    K11Kernel kernel;
+    uint32_t depth, waves;
+};
+
+static K11Shape k11_shape(int bpn) {
+#define K11_ROW(BPN)                                                                            \
+    if (bpn == BPN)                                                                             \
+        return {k11_stage<BPN, k3_tile_t(BPN), k11_depth(BPN), k11_waves(BPN)>, k11_depth(BPN), \
+                k11_waves(BPN)};
+    K11_BPNS(K11_ROW)
+#undef K11_ROW
+    return {nullptr, 0, 0};
+}
+
+void xhip_k11_plan(uint64_t len, int bpn, uint32_t n, XhipK11Plan* plan) {
+    *plan = XhipK11Plan{};
+    const K11Shape shape = k11_shape(bpn);
+    if (!shape.kernel || len == 0 || len > 0xffffffffu || n == 0) return;
+    plan->tile_elems = 64 * k3_tile_t(bpn);
+    plan->depth = shape.depth;
+    plan->waves = shape.waves;
+    plan->span = K11_SPAN;
+    plan->n_tiles = len / plan->tile_elems;
+    plan->tile_blocks = ceil_div_u32(plan->n_tiles, shape.waves * K11_SPAN);
+    plan->copy_bytes = k8_round_up(len * uint64_t(bpn), 16);
+    plan->has_tail = plan->n_tiles * plan->tile_elems * uint64_t(bpn) < plan->copy_bytes ? 1 : 0;
+    plan->bad_off = k8_round_up(8 * uint64_t(n), 64);
+    plan->work_bytes = plan->bad_off + 4 * uint64_t(n);
+}
+
+// 0 < order < 2^(8 * bpn)
+static bool k11_order_fits(const XhipK11Order& order, int bpn) {
+    bool any = false;
+    for (int j = 0; j < 10; ++j) {
+        const int bits = 8 * bpn - 32 * j;  // of word j that an element has
+        if (bits < 32 && (bits <= 0 ? order.w[j] : order.w[j] >> bits)) return false;
+        any = any || order.w[j];
+    }
+    return any;
+}
+
+hipError_t xhip_k11_stage_run(const uint8_t* src, uint64_t src_bytes, const uint64_t* offs,
+                              uint32_t n, uint64_t len, int bpn, XhipK11Order order,
+                              uint8_t* pool, uint64_t pool_bytes, uint64_t stride, uint64_t row,
+                              void* work, uint64_t work_bytes) {
+    if (n == 0) return hipSuccess;
+    XhipK11Plan plan;
+    xhip_k11_plan(len, bpn, n, &plan);
+    if (plan.work_bytes == 0 || !k11_order_fits(order, bpn) || !src || !offs || !pool || !work ||
+        reinterpret_cast<uintptr_t>(src) % 16 || reinterpret_cast<uintptr_t>(pool) % 16 ||
+        reinterpret_cast<uintptr_t>(work) % 16 || stride % 16 || stride < plan.copy_bytes ||
+        work_bytes < plan.work_bytes)
+        return hipErrorInvalidValue;
+    // every byte the kernels touch: copy_bytes from each offset, and the rows
+    for (uint32_t i = 0; i < n; ++i)
+        if (offs[i] % 16 || offs[i] > src_bytes || plan.copy_bytes > src_bytes - offs[i])
+            return hipErrorInvalidValue;
+    if (row > pool_bytes / stride) return hipErrorInvalidValue;
+    const uint64_t room = pool_bytes - row * stride;
+    if (n - 1 > room / stride || plan.copy_bytes > room - (n - 1) * stride)
+        return hipErrorInvalidValue;
+
+    // the offsets and the cleared `bad` words in one copy
+    std::vector<uint8_t> up(plan.work_bytes, 0);
+    std::memcpy(up.data(), offs, 8 * uint64_t(n));
+    hipError_t e = hipMemcpy(work, up.data(), up.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return e;
+    const uint64_t* dev_offs = static_cast<const uint64_t*>(work);
+    uint32_t* bad = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(work) + plan.bad_off);
+    uint8_t* rows = pool + row * stride;
+    const K11Shape shape = k11_shape(bpn);
+    for (uint32_t o = 0; o < n; o += 65535) {  // a grid's y extent
+        const uint32_t objs = std::min<uint32_t>(n - o, 65535);
+        hipLaunchKernelGGL(shape.kernel, dim3(plan.tile_blocks + plan.has_tail, objs),
+                           dim3(shape.waves * 64), 0, 0, src, dev_offs + o, rows + o * stride,
+                           stride, len, uint32_t(plan.n_tiles), plan.span, order, bad + o);
+        hipLaunchKernelGGL(k11_wipe, dim3(ceil_div_u32(plan.copy_bytes / 16, 1024), objs),
+                           dim3(256), 0, 0, rows + o * stride, stride, plan.copy_bytes, bad + o);
+    }
     return hipGetLastError();
 }

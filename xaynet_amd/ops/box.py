@@ -414,11 +414,16 @@ class GpuBox:
         signature at 136 verifies over round_seed || "sum"; bit 2 (tag 2), the
         update signature at 200 over round_seed || "update". A failed
         signature zeroes nothing; the eligibility threshold stays on the host."""
+        return self._open_messages(sealed, pk, sk, round_seed)[:2]
+
+    def _open_messages(self, sealed, pk, sk, round_seed):
+        """open_messages, and (length, tag, flag byte) of every header whose
+        length field holds, by message."""
         messages, _ = self.sealbox_open_batch(sealed, pk, sk, device_keys=True)
-        flags = [0] * len(messages)
+        flags, headers = [0] * len(messages), {}
         live = [i for i, m in enumerate(messages) if m is not None and m.numel() >= 136]
         if not live:
-            return messages, flags
+            return messages, flags, headers
         data = self.opened_buffer
         offs = [self.opened_offsets[i] for i in live]
         at = torch.tensor(offs, device=self.device)[:, None] + 128 + \
@@ -434,6 +439,7 @@ class GpuBox:
             length = int.from_bytes(bytes(head[:4]), "big")
             if not 136 <= length <= messages[i].numel():
                 continue
+            headers[i] = (length, int(head[4]), int(head[5]))
             jobs.append((i, 1, off, off + 64, length - 64, 0))
             if extra is None or head[5] & 1 or head[4] not in (1, 2, 3):
                 continue
@@ -447,7 +453,24 @@ class GpuBox:
                               [j[4] for j in jobs], [j[5] for j in jobs], data, extra)
             for (i, bit, *_), good in zip(jobs, ok):
                 flags[i] |= bit * good
-        return messages, flags
+        return messages, flags, headers
+
+    def open_updates(self, sealed, pk, sk, round_seed, engine, pool, row=0):
+        """open_messages, then the masked vector of every update message whose
+        three signatures verify (flags 7, tag 2, no multipart chunk) from the
+        opened buffer into `pool` rows from `row` on (K11,
+        `engine.stage_updates`): no plaintext goes to the host. Returns
+        (flags, staged, index): flags as open_messages gives them, staged the
+        engine's result and index[j] the message staged object j came from.
+        The MaskObject starts at byte 264 of a message; the seed dict behind
+        it is not parsed here."""
+        _, flags, headers = self._open_messages(sealed, pk, sk, round_seed)
+        index = [i for i, f in enumerate(flags)
+                 if f == 7 and headers[i][1] == 2 and not headers[i][2] & 1]
+        buffer = self.opened_buffer if index else self._new(0)
+        staged = engine.stage_updates(buffer, [self.opened_offsets[i] + 264 for i in index],
+                                      [headers[i][0] - 264 for i in index], pool, row)
+        return flags, staged, index
 
     # ---------------- the MAC alone ----------------
 

@@ -25,6 +25,7 @@ f64 Bmax orders (2112..2143 bits) are routed to the CPU oracle by the caller.
 import os
 import warnings
 from concurrent.futures import ThreadPoolExecutor
+from dataclasses import dataclass
 
 import numpy as np
 import torch
@@ -38,6 +39,19 @@ try:
 except ImportError as e:  # pragma: no cover
     _hip = None
     _hip_err = e
+
+
+@dataclass
+class StagedUpdates:
+    """What stage_updates did with a batch: `status` an object (0 valid, 1
+    malformed, 2 invalid), the `rows` pool rows it filled from `row` on, the
+    count of `valid` objects and the sum of their unit values mod the unit
+    order."""
+    status: list
+    row: int
+    rows: int
+    valid: int
+    unit_sum: int
 
 
 def gpu_available() -> bool:
@@ -67,6 +81,7 @@ class GpuMaskedAggregator(MaskedAggregatorBase):
         self._enc_work = self._enc_dev = self._enc_pin = None
         # decode_model: cached workspace, device body, output and pinned staging buffer
         self._dec_work = self._dec_dev = self._dec_out = self._dec_pin = None
+        self._stage_work = None  # stage_updates: cached workspace
 
     # ---------------- tensor forms ----------------
 
@@ -167,6 +182,93 @@ class GpuMaskedAggregator(MaskedAggregatorBase):
         )
         self.nb_models += n_updates
         self.unit_acc = (self.unit_acc + unit_sum) % int(self.unit_cfg.order)
+
+    # ---------------- staging from device memory (K11) ----------------
+
+    def stage_updates(self, buffer: torch.Tensor, offsets, avail, pool: torch.Tensor,
+                      row: int = 0) -> StagedUpdates:
+        """Masked vectors that lie in device memory (opened messages, say) into
+        pool rows, checked on the way (K11): the device form of
+        MaskObject.is_valid followed by upload_update. `buffer` is a flat uint8
+        tensor on this engine's device; object i is the MaskObject wire form
+        config(4) | count(u32 BE) | limbs | unit config(4) | unit limb at byte
+        offsets[i], of which avail[i] bytes belong to it. Status 1 (malformed,
+        no row): limbs that do not start on a 16-byte boundary, a config that
+        is not this engine's, a count that is not `length`, or fewer bytes than
+        the object needs. Status 2 (invalid): a unit value that is not below
+        the unit order (no row), or an element that is not below the order
+        (its row is zeros, which add nothing to the digit planes). The others,
+        in order, take rows row, row + 1, ... The pool needs a row from `row`
+        on for every object of the batch: ValueError otherwise, before
+        anything is launched."""
+        if not isinstance(buffer, torch.Tensor) or buffer.dtype != torch.uint8 \
+                or buffer.dim() != 1 or not buffer.is_contiguous() \
+                or buffer.device != self.acc.device:
+            raise ValueError(f"stage_updates takes a flat uint8 tensor on {self.acc.device}")
+        offsets, avail = [int(o) for o in offsets], [int(a) for a in avail]
+        if len(offsets) != len(avail):
+            raise ValueError("stage_updates: one offset and one byte count an object")
+        if pool.dtype != torch.uint8 or pool.dim() != 2 or not pool.is_contiguous() \
+                or pool.device != self.acc.device or pool.shape[1] < self.row_stride():
+            raise ValueError("stage_updates takes a pool of alloc_update_pool")
+        if not 1 <= self.length < 2**32:
+            raise ValueError("a MaskObject counts its elements in 32 bits")
+        if row < 0 or row + len(offsets) > pool.shape[0]:
+            raise ValueError(f"{len(offsets)} objects do not fit the pool's {pool.shape[0]} rows "
+                             f"from row {row} on")
+        ubpn = self.unit_cfg.bytes_per_number
+        limb_bytes = self.length * self.bpn
+        need = 8 + limb_bytes + 4 + ubpn
+        status = [1] * len(offsets)
+        # one gathered read of every candidate's small fields: the head, and
+        # the unit config and limb behind the limbs
+        live = [i for i, (o, a) in enumerate(zip(offsets, avail))
+                if o >= 0 and (o + 8) % 16 == 0 and a >= need and o + need <= buffer.numel()]
+        staged, units = [], []
+        if live:
+            dev = self.acc.device
+            field = torch.cat([torch.arange(8, device=dev),
+                               8 + limb_bytes + torch.arange(4 + ubpn, device=dev)])
+            at = torch.tensor([offsets[i] for i in live], device=dev)[:, None] + field
+            small = buffer[at.reshape(-1)].reshape(len(live), -1).cpu().numpy()
+            head = bytes(self.vect_cfg.to_bytes()) + self.length.to_bytes(4, "big")
+            unit_order = int(self.unit_cfg.order)
+            for i, f in zip(live, small):
+                if f[:8].tobytes() != head or f[8:12].tobytes() != bytes(self.unit_cfg.to_bytes()):
+                    continue
+                unit = int.from_bytes(f[12:].tobytes(), "little")
+                status[i] = 2
+                if unit < unit_order:
+                    staged.append(i)
+                    units.append(unit)
+        unit_sum = 0
+        if staged:
+            with torch.cuda.device(self.acc.device):
+                plan = _hip._stage_plan(self.length, self.bpn, len(staged))
+                work = self._enc_buffer("_stage_work", plan["work_bytes"])
+                _hip._stage_run(buffer.data_ptr(), buffer.numel(),
+                                [offsets[i] + 8 for i in staged], self.length, self.bpn,
+                                self.order, pool.data_ptr(), pool.numel(), pool.stride(0), row,
+                                work.data_ptr(), work.numel())
+                bad = work[plan["bad_off"]:plan["bad_off"] + 4 * len(staged)].view(torch.int32)
+                for i, unit, b in zip(staged, units, bad.tolist()):
+                    status[i] = 2 if b else 0
+                    if not b:
+                        unit_sum = (unit_sum + unit) % unit_order
+        return StagedUpdates(status, row, len(staged), status.count(0), unit_sum)
+
+    def aggregate_staged(self, pool: torch.Tensor, staged: StagedUpdates):
+        """Accumulate what stage_updates left in `pool`: its rows (the zero
+        rows of invalid objects included) go through K3, and the valid objects
+        count as models."""
+        self._check_headroom(staged.valid)
+        if staged.rows:
+            _hip.aggregate_batch(
+                self.acc.data_ptr(), pool[staged.row].data_ptr(), pool.stride(0), staged.rows,
+                self.length, self.bpn, int(os.environ.get("XAYNET_K3_EPT", "0"))
+            )
+        self.nb_models += staged.valid
+        self.unit_acc = (self.unit_acc + staged.unit_sum) % int(self.unit_cfg.order)
 
     # ---------------- finalize / unmask (K2, K4) ----------------
 
