@@ -3,6 +3,7 @@
 // callers pass raw device pointers (torch `tensor.data_ptr()`), and all
 // launches go to the null stream, which serializes with PyTorch's default
 // stream on the device.
+#include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
 
 #include <pybind11/stl.h>
@@ -903,6 +904,67 @@ PYBIND11_MODULE(_hip, m) {
         py::arg("src"), py::arg("src_bytes"), py::arg("offs"), py::arg("len"), py::arg("bpn"),
         py::arg("order"), py::arg("pool"), py::arg("pool_bytes"), py::arg("stride"),
         py::arg("row"), py::arg("work"), py::arg("work_bytes"));
+
+    // private (ops/engine.py): how K12 gathers n objects of len elements of bpn
+    // bytes from n_pieces pieces, and the workspace _gather_run takes
+    // (kernels.h). All zero where there is no such launch.
+    m.def(
+        "_gather_plan",
+        [](uint64_t len, int bpn, uint32_t n, uint64_t n_pieces) {
+            XhipK12Plan p;
+            xhip_k12_plan(len, bpn, n, n_pieces, &p);
+            py::dict d;
+            d["tile_elems"] = p.tile_elems;
+            d["waves"] = p.waves;
+            d["span"] = p.span;
+            d["blocks"] = p.blocks;
+            d["n_tiles"] = p.n_tiles;
+            d["copy_bytes"] = p.copy_bytes;
+            d["piece_off"] = p.piece_off;
+            d["base_off"] = p.base_off;
+            d["bad_off"] = p.bad_off;
+            d["work_bytes"] = p.work_bytes;
+            return d;
+        },
+        py::arg("len"), py::arg("bpn"), py::arg("n"), py::arg("n_pieces"));
+
+    // private (ops/engine.py): K12 over one batch. Object i is the
+    // concatenation of counts[i] pieces of the device buffer `src`; piece j of
+    // the flat tables (arrays of u64) starts at byte piece_src[j] and ends at
+    // row byte piece_end[j]. Rows and `bad` words as _stage_run leaves them. Every
+    // piece and row is checked before any launch (kernels.h).
+    m.def(
+        "_gather_run",
+        [](uintptr_t src, uint64_t src_bytes,
+           const py::array_t<uint64_t, py::array::c_style | py::array::forcecast>& piece_src,
+           const py::array_t<uint64_t, py::array::c_style | py::array::forcecast>& piece_end,
+           const std::vector<uint32_t>& counts, uint64_t len, int bpn, const std::string& order, uintptr_t pool, uint64_t pool_bytes,
+           uint64_t stride, uint64_t row, uintptr_t work, uint64_t work_bytes) {
+            uint64_t total = 0;
+            for (uint32_t c : counts) total += c;
+            if (counts.size() > 0xffffffffu || piece_src.ndim() != 1 || piece_end.ndim() != 1 ||
+                uint64_t(piece_src.size()) != total || uint64_t(piece_end.size()) != total)
+                throw py::value_error("_gather_run: the tables do not match the counts");
+            const Limbs o = parse_limbs(order);
+            XhipK11Order words;
+            for (int j = 0; j < 10; ++j) words.w[j] = uint32_t(o.v.w[j / 2] >> (32 * (j % 2)));
+            hipError_t e;
+            {
+                py::gil_scoped_release release;
+                e = xhip_k12_gather_run(u8p(src), src_bytes, piece_src.data(), piece_end.data(),
+                                        counts.data(), uint32_t(counts.size()), len, bpn, words,
+                                        u8p(pool), pool_bytes, stride, row,
+                                        reinterpret_cast<void*>(work), work_bytes);
+            }
+            if (e == hipErrorInvalidValue)
+                throw py::value_error("_gather_run: the bytes per number, the order, a piece, a "
+                                      "row or the workspace does not fit");
+            check(e, "k12_gather_run");
+        },
+        py::arg("src"), py::arg("src_bytes"), py::arg("piece_src"), py::arg("piece_end"),
+        py::arg("counts"), py::arg("len"), py::arg("bpn"), py::arg("order"), py::arg("pool"),
+        py::arg("pool_bytes"), py::arg("stride"), py::arg("row"), py::arg("work"),
+        py::arg("work_bytes"));
 
     // [n_planes][len] digit planes minus the mask -> model weights.
     // dtype follows mask::DataType: 0=F32 1=F64 2=I32 3=I64

@@ -440,4 +440,35 @@ hipError_t xhip_k11_stage_run(const uint8_t* src, uint64_t src_bytes, const uint
                               uint8_t* pool, uint64_t pool_bytes, uint64_t stride, uint64_t row,
                               void* work, uint64_t work_bytes);
 
+// ---- K12: masked vectors that lie in pieces into rows of the K3 pool ----
+//
+// How a batch of n objects of `len` elements of `bpn` bytes, n_pieces pieces in
+// all, is gathered. The tiles are K11's; a wave walks `span` of them, building
+// each in one of its two LDS slots, and a block is `waves` waves over
+// waves * span adjacent tiles; `blocks` of them cover the n_tiles tiles of an
+// object, the last of which may be partial. The workspace holds the piece
+// table (16 bytes a piece: source byte offset, cumulative row end) at
+// piece_off, the n + 1 table bases of the objects at base_off and one `bad`
+// word an object at bad_off. All zero for a bpn without a kernel, len outside
+// [1, 2^32), n == 0 or n_pieces outside [n, 2^32).
+struct XhipK12Plan {
+    uint32_t tile_elems, waves, span, blocks;
+    uint64_t n_tiles, copy_bytes, piece_off, base_off, bad_off, work_bytes;
+};
+void xhip_k12_plan(uint64_t len, int bpn, uint32_t n, uint64_t n_pieces, XhipK12Plan* plan);
+// Object i is the concatenation of counts[i] pieces, in order; piece j of the
+// flat host tables lies at src + piece_src[j] and ends at row byte
+// piece_end[j]. Output as xhip_k11_stage_run: the row, zeros up to the 16-byte
+// boundary, the `bad` word, zeros over the rows of bad objects. A piece may
+// start at any byte. Only aligned dwords that hold a byte of a piece are read.
+// hipErrorInvalidValue, before any launch, for what xhip_k11_stage_run refuses
+// of bpn, len, order, pool, stride, row and workspace, and for: an object
+// without pieces, ends that do not rise strictly from 0 to len * bpn, a piece
+// of which an aligned dword is not wholly inside src_bytes.
+hipError_t xhip_k12_gather_run(const uint8_t* src, uint64_t src_bytes, const uint64_t* piece_src,
+                               const uint64_t* piece_end, const uint32_t* counts, uint32_t n,
+                               uint64_t len, int bpn, XhipK11Order order, uint8_t* pool,
+                               uint64_t pool_bytes, uint64_t stride, uint64_t row, void* work,
+                               uint64_t work_bytes);
+
 }  // extern "C"

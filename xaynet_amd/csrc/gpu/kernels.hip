@@ -3589,6 +3589,49 @@ __device__ __forceinline__ uint32_t k11_not_below(const uint32_t (&v)[NDIG],
     return 1u - uint32_t(t >> 63);
 }
 
+// The element that starts sh bytes (0..3) into r[0], in LDS: 1 where it is not
+// below the order. (Forced inline: at sixteen call sites of ten digits the
+// compiler would rather call it, with its arrays in scratch.)
+template <int BPN>
+__device__ __forceinline__ uint32_t k11_check(const uint32_t* r, uint32_t sh,
+                                              const XhipK11Order& order) {
+    constexpr int NDIG = (BPN + 3) / 4, NW = (BPN + 6) / 4;
+    uint32_t w[NW], v[NDIG];
+#pragma unroll
+    for (int j = 0; j < NW; ++j) w[j] = r[j];
+#pragma unroll
+    for (int d = 0; d < NDIG; ++d) v[d] = k3_digit<BPN>(w, sh, d);
+    return k11_not_below(v, order);
+}
+
+// A tile's image, complete in the slot s, to the row and through the check;
+// k11_stage and k12_gather share it. o is the tile's place in the row plus this
+// lane's 16 bytes: vector lane + 64p goes out with one coalesced 16-byte store
+// a lane and piece. Then lane l's elements l + 64j are read back out of the
+// slot at rword (+ rsh bytes) and compared; the return is 1 where one is not
+// below the order. FULL is a whole tile; otherwise only the first nvec vectors
+// and nelem elements exist.
+template <int BPN, int T, bool FULL>
+__device__ __forceinline__ uint32_t k11_tile_out(const uint32_t* s, uint8_t* o, uint32_t lane,
+                                                 uint32_t rword, uint32_t rsh, uint32_t nvec,
+                                                 uint32_t nelem, const XhipK11Order& order) {
+    constexpr int PIECES = K3Tile<BPN, T>::PIECES;
+#pragma unroll
+    for (int p = 0; p < PIECES; ++p) {
+        // at most eight pieces in registers at a time: the 37 and 39 of the
+        // widest tiles at once would spill
+        if (p % 8 == 0 && p) asm volatile("" ::: "memory");
+        if (FULL || p * 64 + lane < nvec)
+            *reinterpret_cast<u32x4*>(o + p * 1024) =
+                *reinterpret_cast<const u32x4*>(s + p * 256 + lane * 4);
+    }
+    uint32_t over = 0;
+#pragma unroll
+    for (int j = 0; j < T; ++j)
+        if (FULL || j * 64 + lane < nelem) over |= k11_check<BPN>(s + rword + j * 16 * BPN, rsh, order);
+    return over;
+}
+
 // The ring depth and the waves of a block per bytes-per-number: three slots
 // where a tile is at most 8 KiB, else two, and as many waves, up to four, as
 // keep the rings of two blocks inside a CU's 160 KiB of LDS.
@@ -3620,16 +3663,8 @@ __global__ __launch_bounds__(WAVES * 64) void k11_stage(
     const bool has_tail = tiled < copy_bytes;  // then block 0 is the tail block
 
     uint32_t over = 0;
-    // the element that starts sh bytes into r[0], in LDS
-    // (forced inline: at sixteen call sites of ten digits the compiler would
-    // rather call it, with its arrays in scratch)
     auto check = [&](const uint32_t* r, uint32_t sh) __attribute__((always_inline)) {
-        uint32_t w[NW], v[NDIG];
-#pragma unroll
-        for (int j = 0; j < NW; ++j) w[j] = r[j];
-#pragma unroll
-        for (int d = 0; d < NDIG; ++d) v[d] = k3_digit<BPN>(w, sh, d);
-        over |= k11_not_below(v, order);
+        over |= k11_check<BPN>(r, sh, order);
     };
 
     if (has_tail && blockIdx.x == 0) {
@@ -3663,18 +3698,9 @@ __global__ __launch_bounds__(WAVES * 64) void k11_stage(
                                          wring + slot * SLOT_WORDS);
             };
             auto handle = [&](uint32_t k, uint32_t slot) __attribute__((always_inline)) {
-                const uint32_t* s = wring + slot * SLOT_WORDS;
-                uint8_t* o = out + at + uint64_t(k) * (WAVES * TILE_BYTES);
-#pragma unroll
-                for (int p = 0; p < PIECES; ++p) {
-                    // at most eight pieces in registers at a time: the 37 and
-                    // 39 of the widest tiles at once would spill
-                    if (p % 8 == 0 && p) asm volatile("" ::: "memory");
-                    *reinterpret_cast<u32x4*>(o + p * 1024) =
-                        *reinterpret_cast<const u32x4*>(s + p * 256 + lane * 4);
-                }
-#pragma unroll
-                for (int j = 0; j < T; ++j) check(s + rword + j * 16 * BPN, rsh);
+                over |= k11_tile_out<BPN, T, true>(wring + slot * SLOT_WORDS,
+                                                   out + at + uint64_t(k) * (WAVES * TILE_BYTES),
+                                                   lane, rword, rsh, PIECES * 64, 64 * T, order);
             };
             auto next = [](uint32_t slot) { return slot + 1 == D ? 0u : slot + 1; };
 
@@ -3811,6 +3837,239 @@ hipError_t xhip_k11_stage_run(const uint8_t* src, uint64_t src_bytes, const uint
         hipLaunchKernelGGL(shape.kernel, dim3(plan.tile_blocks + plan.has_tail, objs),
                            dim3(shape.waves * 64), 0, 0, src, dev_offs + o, rows + o * stride,
                            stride, len, uint32_t(plan.n_tiles), plan.span, order, bad + o);
+        hipLaunchKernelGGL(k11_wipe, dim3(ceil_div_u32(plan.copy_bytes / 16, 1024), objs),
+                           dim3(256), 0, 0, rows + o * stride, stride, plan.copy_bytes, bad + o);
+    }
+    return hipGetLastError();
+}
+
+// ------------------------- K12: multipart update chunks into the K3 pool
+//
+// A multipart update reaches the device as chunk messages, so its masked
+// vector is a concatenation of pieces that lie anywhere in the opened buffer,
+// at any byte offset. k12_gather builds K11's output from them: the row and the
+// verdict on its elements. The grid and the ownership of tiles are K11's; what
+// differs is how a tile comes into its LDS slot. LDS-DMA cannot shift a lane's
+// 16 bytes, so the wave assembles the tile's image itself: it finds the first
+// piece that overlaps the tile by a binary search over the cumulative ends and
+// walks the pieces from there. Of a piece's part [a, b) of the row, the
+// 16-byte row vectors that lie wholly inside are built in registers from
+// aligned source dwords (five of them and v_alignbyte_b32; the shift is the
+// same for the whole part, hence wave-uniform) and written with one 16-byte
+// LDS store each; the bytes before the first and after the last whole vector,
+// at most 15 each, go by byte loads and byte LDS stores, so any number of
+// pieces may meet in one vector and an element may be cut anywhere. The image
+// then goes through k11_tile_out like a K11 tile. The last tile of a row may
+// be partial: the same routine with a shorter range and zeros up to the
+// 16-byte boundary. Only the issuing wave touches its two slots: no barriers.
+
+struct XhipK12Piece {
+    uint64_t src;  // byte offset of the piece in the buffer
+    uint64_t end;  // row byte offset just past the piece
+};
+
+// as many waves, up to four, as keep two slots a wave of two blocks inside a
+// CU's 160 KiB of LDS
+constexpr int k12_waves(int bpn) {
+    const int w = 80 * 1024 / (2 * (64 * k3_tile_t(bpn) * bpn + 16));
+    return w > 4 ? 4 : w < 1 ? 1 : w;
+}
+#define K12_SPAN 8    // tiles a wave walks
+#define K12_FLIGHT 4  // whole vectors a lane has in flight: 20 dwords
+
+template <int BPN, int T, int WAVES>
+__global__ __launch_bounds__(WAVES * 64) void k12_gather(
+    const uint8_t* __restrict__ src, const XhipK12Piece* __restrict__ pieces,
+    const uint32_t* __restrict__ bases, uint8_t* __restrict__ rows, uint64_t stride,
+    uint64_t len, uint32_t n_tiles, uint32_t span, XhipK11Order order,
+    uint32_t* __restrict__ bad) {
+    using Tile = K3Tile<BPN, T>;
+    constexpr uint32_t TILE_BYTES = Tile::TILE_BYTES, SLOT_WORDS = Tile::SLOT_WORDS;
+    __shared__ __attribute__((aligned(16))) uint32_t ring[WAVES * 2 * SLOT_WORDS];
+
+    const uint32_t obj = blockIdx.y;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t first = blockIdx.x * (WAVES * span) + wave;
+    if (first >= n_tiles) return;  // wave-uniform; there is no barrier below
+    const uint32_t cnt = min(span, (n_tiles - first + WAVES - 1) / WAVES);
+    const uint32_t pbeg = bases[obj], pend = bases[obj + 1];
+    uint8_t* const out = rows + uint64_t(obj) * stride;
+    const uint64_t row_bytes = len * BPN, copy_bytes = (row_bytes + 15) & ~uint64_t(15);
+    uint32_t* const wring = ring + wave * (2 * SLOT_WORDS);
+    const uint32_t rword = (lane * BPN) >> 2, rsh = (lane * BPN) & 3;
+
+    // The image of the row bytes [t0, t1) into the slot at s.
+    auto gather = [&](uint64_t t0, uint64_t t1, uint32_t* s) {
+        uint8_t* const sb = reinterpret_cast<uint8_t*>(s);
+        // first piece that ends behind t0 (the pieces cover the row: there is one)
+        uint32_t lo = pbeg, hi = pend - 1;
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (pieces[mid].end > t0) hi = mid; else lo = mid + 1;
+        }
+        uint64_t start = lo == pbeg ? 0 : pieces[lo - 1].end;
+        for (uint32_t i = lo; i < pend && start < t1; ++i) {
+            const XhipK12Piece pc = pieces[i];
+            const uint64_t a = max(start, t0), b = min(pc.end, t1);
+            const uint8_t* const from = src + pc.src;  // of row byte `start`
+            // whole vectors [v0, v1), the partial ones [a, hend) and [ts, b)
+            const uint64_t v0 = (a + 15) & ~uint64_t(15), v1 = b & ~uint64_t(15);
+            const uint64_t hend = min(b, v0), ts = max(v1, hend);
+            if (v0 < v1) {
+                const uint32_t nv = uint32_t(v1 - v0) >> 4;
+                const uint8_t* const g = from + (v0 - start);
+                const uint32_t sh = uint32_t(reinterpret_cast<uintptr_t>(g)) & 3;  // of every vector
+                const uint32_t* const gw = reinterpret_cast<const uint32_t*>(g - sh);
+                uint32_t* const lw = s + (uint32_t(v0 - t0) >> 2);
+                for (uint32_t j0 = 0; j0 < nv; j0 += 64 * K12_FLIGHT) {
+                    uint32_t d[K12_FLIGHT][5];
+#pragma unroll
+                    for (int u = 0; u < K12_FLIGHT; ++u) {
+                        const uint32_t j = j0 + 64 * u + lane;
+                        if (j < nv) {
+#pragma unroll
+                            for (int q = 0; q < 4; ++q) d[u][q] = gw[4 * j + q];
+                            // the fifth dword holds bytes of the vector only where shifted
+                            d[u][4] = sh ? gw[4 * j + 4] : 0u;
+                        }
+                    }
+#pragma unroll
+                    for (int u = 0; u < K12_FLIGHT; ++u) {
+                        const uint32_t j = j0 + 64 * u + lane;
+                        if (j < nv) {
+                            u32x4 x;
+                            x[0] = __builtin_amdgcn_alignbyte(d[u][1], d[u][0], sh);
+                            x[1] = __builtin_amdgcn_alignbyte(d[u][2], d[u][1], sh);
+                            x[2] = __builtin_amdgcn_alignbyte(d[u][3], d[u][2], sh);
+                            x[3] = __builtin_amdgcn_alignbyte(d[u][4], d[u][3], sh);
+                            *reinterpret_cast<u32x4*>(lw + 4 * j) = x;
+                        }
+                    }
+                }
+            }
+            // at most 15 bytes either side, one a lane
+            const uint32_t h = uint32_t(hend - a), tl = uint32_t(b - ts);
+            if (lane < h + tl) {
+                const uint64_t x = lane < h ? a + lane : ts + (lane - h);
+                sb[uint32_t(x - t0)] = from[x - start];
+            }
+            start = pc.end;
+        }
+    };
+
+    uint32_t over = 0;
+    for (uint32_t k = 0; k < cnt; ++k) {
+        const uint32_t tile = first + k * WAVES;
+        const uint64_t t0 = uint64_t(tile) * TILE_BYTES;
+        const uint64_t t1 = min(t0 + TILE_BYTES, row_bytes), img = min(t0 + TILE_BYTES, copy_bytes);
+        uint32_t* const s = wring + (k & 1) * SLOT_WORDS;
+        gather(t0, t1, s);
+        if (lane < uint32_t(img - t1))  // the row's zeros up to the 16-byte boundary
+            reinterpret_cast<uint8_t*>(s)[uint32_t(t1 - t0) + lane] = 0;
+        // the image is complete once the wave's LDS stores are: then other
+        // lanes' bytes may be read
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        uint8_t* const o = out + t0 + lane * 16;
+        if (t1 - t0 == TILE_BYTES)
+            over |= k11_tile_out<BPN, T, true>(s, o, lane, rword, rsh, 0, 0, order);
+        else
+            over |= k11_tile_out<BPN, T, false>(s, o, lane, rword, rsh, uint32_t(img - t0) >> 4,
+                                                uint32_t(len - uint64_t(tile) * (64 * T)), order);
+    }
+    // one ballot a wave, and one atomic only where an element was out of range
+    if (__ballot(over != 0) != 0 && lane == 0) atomicOr(bad + obj, 1u);
+}
+
+using K12Kernel = void (*)(const uint8_t*, const XhipK12Piece*, const uint32_t*, uint8_t*,
+                           uint64_t, uint64_t, uint32_t, uint32_t, XhipK11Order, uint32_t*);
+struct K12Shape {
+    K12Kernel kernel;
+    uint32_t waves;
+};
+
+static K12Shape k12_shape(int bpn) {
+#define K12_ROW(BPN) \
+    if (bpn == BPN) return {k12_gather<BPN, k3_tile_t(BPN), k12_waves(BPN)>, k12_waves(BPN)};
+    K11_BPNS(K12_ROW)
+#undef K12_ROW
+    return {nullptr, 0};
+}
+
+void xhip_k12_plan(uint64_t len, int bpn, uint32_t n, uint64_t n_pieces, XhipK12Plan* plan) {
+    *plan = XhipK12Plan{};
+    const K12Shape shape = k12_shape(bpn);
+    if (!shape.kernel || len == 0 || len > 0xffffffffu || n == 0 || n_pieces < n ||
+        n_pieces > 0xffffffffu)
+        return;
+    plan->tile_elems = 64 * k3_tile_t(bpn);
+    plan->waves = shape.waves;
+    plan->span = K12_SPAN;
+    plan->n_tiles = (len + plan->tile_elems - 1) / plan->tile_elems;
+    plan->blocks = ceil_div_u32(plan->n_tiles, shape.waves * K12_SPAN);
+    plan->copy_bytes = k8_round_up(len * uint64_t(bpn), 16);
+    plan->piece_off = 0;
+    plan->base_off = k8_round_up(16 * n_pieces, 64);
+    plan->bad_off = k8_round_up(plan->base_off + 4 * (uint64_t(n) + 1), 64);
+    plan->work_bytes = plan->bad_off + 4 * uint64_t(n);
+}
+
+hipError_t xhip_k12_gather_run(const uint8_t* src, uint64_t src_bytes, const uint64_t* piece_src,
+                               const uint64_t* piece_end, const uint32_t* counts, uint32_t n,
+                               uint64_t len, int bpn, XhipK11Order order, uint8_t* pool,
+                               uint64_t pool_bytes, uint64_t stride, uint64_t row, void* work,
+                               uint64_t work_bytes) {
+    if (n == 0) return hipSuccess;
+    if (!counts) return hipErrorInvalidValue;
+    uint64_t n_pieces = 0;
+    for (uint32_t i = 0; i < n; ++i) n_pieces += counts[i];
+    XhipK12Plan plan;
+    xhip_k12_plan(len, bpn, n, n_pieces, &plan);
+    if (plan.work_bytes == 0 || !k11_order_fits(order, bpn) || !src || !piece_src || !piece_end ||
+        !pool || !work || reinterpret_cast<uintptr_t>(src) % 16 ||
+        reinterpret_cast<uintptr_t>(pool) % 16 || reinterpret_cast<uintptr_t>(work) % 16 ||
+        stride % 16 || stride < plan.copy_bytes || work_bytes < plan.work_bytes)
+        return hipErrorInvalidValue;
+    // The tables, the bases and the cleared `bad` words, checked as they are
+    // laid out: every object's ends rise from 0 to len * bpn, and every aligned
+    // dword with a byte of a piece lies inside the buffer.
+    std::vector<uint8_t> up(plan.work_bytes, 0);
+    XhipK12Piece* table = reinterpret_cast<XhipK12Piece*>(up.data() + plan.piece_off);
+    uint32_t* base = reinterpret_cast<uint32_t*>(up.data() + plan.base_off);
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        base[i] = uint32_t(at);
+        uint64_t prev = 0;
+        if (counts[i] == 0) return hipErrorInvalidValue;
+        for (uint32_t j = 0; j < counts[i]; ++j, ++at) {
+            const uint64_t s = piece_src[at], e = piece_end[at];
+            if (e <= prev || e > len * uint64_t(bpn) || s > src_bytes ||
+                e - prev > src_bytes - s || k8_round_up(s + (e - prev), 4) > src_bytes)
+                return hipErrorInvalidValue;
+            table[at] = XhipK12Piece{s, e};
+            prev = e;
+        }
+        if (prev != len * uint64_t(bpn)) return hipErrorInvalidValue;
+    }
+    base[n] = uint32_t(at);
+    if (row > pool_bytes / stride) return hipErrorInvalidValue;
+    const uint64_t room = pool_bytes - row * stride;
+    if (n - 1 > room / stride || plan.copy_bytes > room - (n - 1) * stride)
+        return hipErrorInvalidValue;
+
+    hipError_t e = hipMemcpy(work, up.data(), up.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return e;
+    uint8_t* const w = static_cast<uint8_t*>(work);
+    const XhipK12Piece* dev_table = reinterpret_cast<const XhipK12Piece*>(w + plan.piece_off);
+    const uint32_t* dev_base = reinterpret_cast<const uint32_t*>(w + plan.base_off);
+    uint32_t* bad = reinterpret_cast<uint32_t*>(w + plan.bad_off);
+    uint8_t* rows = pool + row * stride;
+    const K12Shape shape = k12_shape(bpn);
+    for (uint32_t o = 0; o < n; o += 65535) {  // a grid's y extent
+        const uint32_t objs = std::min<uint32_t>(n - o, 65535);
+        hipLaunchKernelGGL(shape.kernel, dim3(plan.blocks, objs), dim3(shape.waves * 64), 0, 0,
+                           src, dev_table, dev_base + o, rows + o * stride, stride, len,
+                           uint32_t(plan.n_tiles), plan.span, order, bad + o);
         hipLaunchKernelGGL(k11_wipe, dim3(ceil_div_u32(plan.copy_bytes / 16, 1024), objs),
                            dim3(256), 0, 0, rows + o * stride, stride, plan.copy_bytes, bad + o);
     }

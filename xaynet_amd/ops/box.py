@@ -53,6 +53,44 @@ def _layout(lens):
     return offs, at + _HEAD
 
 
+def chunk_sets(entries):
+    """Group the messages of a batch into complete updates by the multipart
+    rule of Coordinator::handle_message_bytes, applied message by message in
+    batch order. entries[i] is (participant pk, tag, multipart flag, chunk id,
+    message id, last flag, data length) of a message whose header signature
+    verified. Returns (sets, host_sets, pending): every complete set as the
+    list of its entry indices in chunk order, in order of completion; of those,
+    the multipart sets whose chunk 0 carries fewer than 136 data bytes (its
+    task signatures straddle chunks) apart in host_sets; and the indices, in
+    batch order, of the chunks whose set is still open at the end. A message
+    that is no chunk is a set of one. The key of a set is (pk, message id); a
+    duplicate id overwrites the earlier chunk; two different last ids corrupt
+    the set, as do ids other than 0..last once last + 1 chunks are there, and a
+    corrupt set's chunks appear nowhere; chunks behind a completion start a
+    new set."""
+    sets, host_sets, open_sets = [], [], {}
+    for i, (pk, _tag, multipart, cid, mid, last, _n) in enumerate(entries):
+        if not multipart:
+            sets.append([i])
+            continue
+        key = (bytes(pk), mid)
+        chunks, last_id = open_sets.get(key, ({}, -1))
+        chunks[cid] = i
+        if last:
+            if last_id >= 0 and last_id != cid:
+                open_sets.pop(key, None)
+                continue
+            last_id = cid
+        open_sets[key] = (chunks, last_id)
+        if last_id >= 0 and len(chunks) == last_id + 1:
+            del open_sets[key]
+            if sorted(chunks) == list(range(last_id + 1)):
+                done = [chunks[c] for c in range(last_id + 1)]
+                (sets if entries[done[0]][6] >= 136 else host_sets).append(done)
+    pending = sorted(i for chunks, _ in open_sets.values() for i in chunks.values())
+    return sets, host_sets, pending
+
+
 class GpuBox:
     """Seal and open batches of boxes on one GPU. `kernel_ms` is the device
     time of the last batch's kernels when `time_kernels` is set. After an
@@ -471,6 +509,70 @@ class GpuBox:
         staged = engine.stage_updates(buffer, [self.opened_offsets[i] + 264 for i in index],
                                       [headers[i][0] - 264 for i in index], pool, row)
         return flags, staged, index
+
+    def open_update_sets(self, sealed, pk, sk, round_seed, engine, pool, row=0):
+        """open_updates for updates that come as multipart chunks as well:
+        the chunks of a batch are grouped into sets (`chunk_sets`), and the
+        masked vector of every complete set is gathered from where its chunks
+        lie in the opened buffer into a `pool` row (K12,
+        `engine.stage_segments`). A single-part update is a set of one and
+        takes the same path. Returns (flags, staged, index, pending,
+        host_sets): flags as open_messages gives them, staged the engine's
+        result, index[j] the messages, in chunk order, staged object j came
+        from, pending the chunk messages whose set is not complete in this
+        batch (nothing is kept between calls: the caller resubmits them with
+        the rest, or hands them to the CPU path), and host_sets the complete
+        sets whose chunk 0 is too short to hold both task signatures, which
+        are not staged. A set is staged when every chunk's header signature
+        verifies and has tag 2 and the sum and update signatures, at bytes 144
+        and 208 of chunk 0, verify (a second K10 call). The seed dict behind
+        the object is not parsed here."""
+        _, flags, headers = self._open_messages(sealed, pk, sk, round_seed)
+        live = [i for i, f in enumerate(flags) if f & 1 and
+                (not headers[i][2] & 1 or headers[i][0] >= 144)]
+        data = self.opened_buffer if live else self._new(0)
+        entries = []
+        if live:
+            # the participant key, length | tag | flags, and the chunk header
+            field = torch.tensor(list(range(64, 96)) + list(range(128, 134)) +
+                                 list(range(136, 141)), device=self.device)
+            at = torch.tensor([self.opened_offsets[i] for i in live],
+                              device=self.device)[:, None] + field
+            for i, f in zip(live, data[at.reshape(-1)].reshape(len(live), -1).cpu().numpy()):
+                multi = int(f[37]) & 1
+                entries.append((f[:32].tobytes(), int(f[36]), multi,
+                                int.from_bytes(f[38:40].tobytes(), "big"),
+                                int.from_bytes(f[40:42].tobytes(), "big"), int(f[42]) & 1,
+                                headers[i][0] - (144 if multi else 136)))
+        sets, host_sets, pending = chunk_sets(entries)
+        sets = [s for s in sets if all(entries[e][1] == 2 for e in s)]
+        off = [self.opened_offsets[i] for i in live]
+        multi = [s for s in sets if entries[s[0]][2]]
+        good = {id(s): flags[live[s[0]]] == 7 for s in sets if not entries[s[0]][2]}
+        if multi:
+            tasks = [bytes(round_seed) + b"sum", bytes(round_seed) + b"update"]
+            task_offs = [0, (len(tasks[0]) + 63) // 64 * 64]
+            extra = self._pack(tasks, task_offs, 0, task_offs[1] + len(tasks[1]) + _HEAD)
+            heads = [off[s[0]] for s in multi for _ in range(2)]
+            ok = self._verify([h + 144 + 64 * (j & 1) for j, h in enumerate(heads)],
+                              [h + 64 for h in heads], task_offs * len(multi),
+                              [len(tasks[0]), len(tasks[1])] * len(multi), [1] * len(heads),
+                              data, extra)
+            for j, s in enumerate(multi):
+                good[id(s)] = bool(ok[2 * j] and ok[2 * j + 1])
+        sets = [s for s in sets if good[id(s)]]
+        objects = []
+        for s in sets:
+            if entries[s[0]][2]:
+                # the chunks' data, less the two task signatures in front
+                pieces = [(off[e] + 144, entries[e][6]) for e in s]
+                pieces[0] = (pieces[0][0] + 128, pieces[0][1] - 128)
+            else:
+                pieces = [(off[s[0]] + 264, entries[s[0]][6] - 128)]
+            objects.append(pieces)
+        staged = engine.stage_segments(data, objects, pool, row)
+        return (flags, staged, [[live[e] for e in s] for s in sets],
+                [live[e] for e in pending], [[live[e] for e in s] for s in host_sets])
 
     # ---------------- the MAC alone ----------------
 

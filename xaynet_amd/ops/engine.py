@@ -257,6 +257,93 @@ class GpuMaskedAggregator(MaskedAggregatorBase):
                         unit_sum = (unit_sum + unit) % unit_order
         return StagedUpdates(status, row, len(staged), status.count(0), unit_sum)
 
+    # ---------------- gathering from pieces (K12) ----------------
+
+    def stage_segments(self, buffer: torch.Tensor, objects, pool: torch.Tensor,
+                       row: int = 0) -> StagedUpdates:
+        """stage_updates for objects that lie in pieces (the chunks of a
+        multipart update, say), gathered into their pool rows and checked on
+        the way (K12). objects[i] is a list of (offset, nbytes) pieces of
+        `buffer` in payload order; their concatenation is the MaskObject wire
+        form, possibly followed by more bytes. A piece may start at any byte
+        and have any length; empty ones are dropped. Statuses, rows, unit_sum
+        and aggregate_staged are as for stage_updates, without its 16-byte
+        rule; status 1 also covers pieces that sum to fewer bytes than the
+        object needs. ValueError, before anything is launched, for a piece
+        outside the buffer, a pool without a row for every object, or a wrong
+        tensor form."""
+        if not isinstance(buffer, torch.Tensor) or buffer.dtype != torch.uint8 \
+                or buffer.dim() != 1 or not buffer.is_contiguous() \
+                or buffer.device != self.acc.device:
+            raise ValueError(f"stage_segments takes a flat uint8 tensor on {self.acc.device}")
+        if pool.dtype != torch.uint8 or pool.dim() != 2 or not pool.is_contiguous() \
+                or pool.device != self.acc.device or pool.shape[1] < self.row_stride():
+            raise ValueError("stage_segments takes a pool of alloc_update_pool")
+        if not 1 <= self.length < 2**32:
+            raise ValueError("a MaskObject counts its elements in 32 bits")
+        if row < 0 or row + len(objects) > pool.shape[0]:
+            raise ValueError(f"{len(objects)} objects do not fit the pool's {pool.shape[0]} rows "
+                             f"from row {row} on")
+        ubpn = self.unit_cfg.bytes_per_number
+        limb_bytes = self.length * self.bpn
+        need = 8 + limb_bytes + 4 + ubpn
+        # the small fields' places in the object: the head, and the unit config
+        # and limb behind the limbs
+        field = np.concatenate([np.arange(8), 8 + limb_bytes + np.arange(4 + ubpn)])
+        status = [1] * len(objects)
+        live, maps, at = [], [], []
+        for i, pieces in enumerate(objects):
+            pc = np.asarray(pieces, dtype=np.int64).reshape(-1, 2)
+            if (pc < 0).any() or (pc.sum(axis=1) > buffer.numel()).any():
+                raise ValueError(f"stage_segments: a piece of object {i} lies outside the buffer")
+            pc = pc[pc[:, 1] > 0]
+            ends = np.cumsum(pc[:, 1])
+            if not len(pc) or ends[-1] < need:
+                continue
+            starts = ends - pc[:, 1]
+            # where each field byte lies: the piece it falls in, whatever
+            # boundaries the field straddles
+            of = np.searchsorted(ends, field, side="right")
+            at.append(pc[of, 0] + field - starts[of])
+            live.append(i)
+            maps.append((pc[:, 0], starts, ends))
+        staged, units, tables = [], [], []
+        if live:
+            dev = self.acc.device
+            idx = torch.from_numpy(np.concatenate(at)).to(dev)
+            small = buffer[idx].reshape(len(live), -1).cpu().numpy()
+            head = bytes(self.vect_cfg.to_bytes()) + self.length.to_bytes(4, "big")
+            unit_order = int(self.unit_cfg.order)
+            for i, f, (offs, starts, ends) in zip(live, small, maps):
+                if f[:8].tobytes() != head or f[8:12].tobytes() != bytes(self.unit_cfg.to_bytes()):
+                    continue
+                unit = int.from_bytes(f[12:].tobytes(), "little")
+                status[i] = 2
+                if unit < unit_order:
+                    # the pieces cut to the limbs, object bytes [8, 8 + limb_bytes)
+                    a, b = np.maximum(starts, 8), np.minimum(ends, 8 + limb_bytes)
+                    keep = b > a
+                    tables.append((offs[keep] + (a - starts)[keep], b[keep] - 8))
+                    staged.append(i)
+                    units.append(unit)
+        unit_sum = 0
+        if staged:
+            counts = [len(t[0]) for t in tables]
+            with torch.cuda.device(self.acc.device):
+                plan = _hip._gather_plan(self.length, self.bpn, len(staged), sum(counts))
+                work = self._enc_buffer("_stage_work", plan["work_bytes"])
+                _hip._gather_run(buffer.data_ptr(), buffer.numel(),
+                                 np.concatenate([t[0] for t in tables]).astype(np.uint64),
+                                 np.concatenate([t[1] for t in tables]).astype(np.uint64), counts,
+                                 self.length, self.bpn, self.order, pool.data_ptr(), pool.numel(),
+                                 pool.stride(0), row, work.data_ptr(), work.numel())
+                bad = work[plan["bad_off"]:plan["bad_off"] + 4 * len(staged)].view(torch.int32)
+                for i, unit, b in zip(staged, units, bad.tolist()):
+                    status[i] = 2 if b else 0
+                    if not b:
+                        unit_sum = (unit_sum + unit) % unit_order
+        return StagedUpdates(status, row, len(staged), status.count(0), unit_sum)
+
     def aggregate_staged(self, pool: torch.Tensor, staged: StagedUpdates):
         """Accumulate what stage_updates left in `pool`: its rows (the zero
         rows of invalid objects included) go through K3, and the valid objects
